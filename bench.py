@@ -3,6 +3,12 @@
 blocks pipelined across N MI355X GPUs over RCCL/xGMI (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W [--model llama-2-70b]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints one JSON result line.
+--dump-outputs DIR also writes the last timed step's outputs as DIR/*.npy so
+two builds can be compared output for output (inputs and weights are seeded).
+--full is reserved for secondary measurements, which never run by default.
 
 For N>1 the driver launches this under torch.distributed.run with one rank per
 GPU; rank r hosts a contiguous span of the 80 blocks (the petals_amd span
@@ -30,6 +36,33 @@ import torch
 def log(msg):
     if int(os.environ.get("RANK", "0")) == 0:
         print(msg, flush=True)
+
+
+DUMP_MAX_BYTES = 64 * 1024 * 1024  # cap on the total size of --dump-outputs files
+
+
+def _dump_outputs(args, outputs):
+    """Write what the timed path returned in its last step as <name>.npy
+    (float32; token ids as float64) under --dump-outputs. Inputs and weights
+    are seeded, so two builds run with the same arguments compare output for
+    output. (The GPU path picks its split-K counts by timing at load; a run that
+    picks other counts rounds differently, and greedy decoding of random-init
+    weights then yields other tokens.) An array that would push the total past DUMP_MAX_BYTES is reduced
+    to a fixed, seeded sample of its elements."""
+    import numpy as np
+
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    budget = DUMP_MAX_BYTES
+    for i, (name, t) in enumerate(sorted(outputs.items())):
+        t = t.detach().cpu()
+        arr = (t.double() if not t.is_floating_point() else t.float()).contiguous().numpy()
+        share = budget // (len(outputs) - i)
+        if arr.nbytes > share:
+            idx = np.random.default_rng(1234).choice(arr.size, share // arr.itemsize, replace=False)
+            arr = arr.reshape(-1)[np.sort(idx)]
+        budget -= arr.nbytes
+        np.save(os.path.join(args.dump_outputs, f"{name}.npy"), arr)
+        log(f"[bench] wrote {name}.npy {arr.dtype} {list(arr.shape)}")
 
 
 def _emit_result(args, world, use_cuda, elapsed, B, stack):
@@ -160,6 +193,7 @@ def run_serve_stack(args, rank, world, use_cuda, config) -> bool:
 
     elapsed = 0.0
     client_ok = True
+    outputs = {}
     if rank == 0:
         model = None
         try:
@@ -176,6 +210,10 @@ def run_serve_stack(args, rank, world, use_cuda, config) -> bool:
             if use_cuda:
                 prompt = prompt.to(device)
             max_len = args.prompt_len + args.warmup + args.steps + 8
+            last = {}
+            if args.dump_outputs:
+                # keep a handle on each forward's logits; the last timed step's survive
+                model.register_forward_hook(lambda _m, _a, res: last.__setitem__("logits", res.logits))
             with model.transformer.h.inference_session(max_length=max_len, batch_size=B) as sess, \
                     model.transformer.h.use_session(sess):
                 out = model.generate(prompt, max_new_tokens=max(args.warmup, 1), do_sample=False,
@@ -191,6 +229,9 @@ def run_serve_stack(args, rank, world, use_cuda, config) -> bool:
                 elapsed = time.perf_counter() - t_start
                 barrier()
                 assert out.shape[1] == args.steps + 1
+                if args.dump_outputs:
+                    # generate() returns [B, 1 + steps]: its input token, then one per timed step
+                    outputs = {"tokens": out, "last_logits": last["logits"][:, -1, :]}
         except Exception as e:  # noqa: BLE001
             print(f"[bench] client failed: {e!r}", flush=True)
             client_ok = False
@@ -214,6 +255,8 @@ def run_serve_stack(args, rank, world, use_cuda, config) -> bool:
         elapsed = float(e.item())
 
     if rank == 0:
+        if args.dump_outputs:
+            _dump_outputs(args, outputs)
         _emit_result(args, world, use_cuda, elapsed, B, "serve")
 
     _serve_cleanup(server, mesh, boot, use_cuda)
@@ -253,6 +296,14 @@ def main():
                    help="serve (default): the REAL serving stack (DHT + Server + handler + client "
                         "sessions) with the RCCL mesh hand-off — what a user gets; pipeline: bare "
                         "rank-per-GPU RCCL pipeline (kernel-harness upper bound)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path returned in its last step "
+                        "(generated tokens, last-step logits) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement; a plain run only sets up, warms up, "
+                        "times --steps steps and prints the result line (there is none yet: other "
+                        "models, batch sizes, precisions and the bare pipeline are selected by their "
+                        "own options, one configuration per run)")
     args = p.parse_args()
 
     import torch.distributed as dist
@@ -287,7 +338,9 @@ def main():
         if run_serve_stack(args, rank, world, use_cuda, config):
             if world > 1:
                 dist.destroy_process_group()
-            os._exit(0)  # skip interpreter-teardown races between HIP and daemon threads
+            # every server/mesh/DHT thread was joined in _serve_cleanup; leave through
+            # the normal interpreter exit so exit handlers and library finalizers run
+            return
         log("[bench] serve stack failed; measuring the bare pipeline instead")
         args.stack = "pipeline"
 
@@ -353,6 +406,8 @@ def main():
             stage.send(h)
             return h  # unused on non-zero ranks
 
+    last_out = {}  # rank 0: logits of the most recent eager head call (--dump-outputs)
+
     def one_token(token_ids, prefix: int):
         """Generate the next token given current ids [B,1] (eager path)."""
         if rank == 0:
@@ -362,6 +417,7 @@ def main():
         out = run_pipeline(h, prefix, 1)
         if rank == 0:
             logits = head_logits(out[:, -1, :])
+            last_out["logits"] = logits
             return logits.argmax(dim=-1, keepdim=True)
         return token_ids
 
@@ -431,7 +487,7 @@ def main():
             if "g_head" in gs:
                 gs["g_head"].replay()
             else:
-                gs["head_eager"]()
+                last_out["logits"] = gs["head_eager"]()
         else:
             dist.recv(gs["h_in"], src=stage.prev_rank)
             gs["g_span"].replay()
@@ -495,6 +551,13 @@ def main():
         elapsed = float(e.item())
 
     if rank == 0:
+        if args.dump_outputs:
+            if use_graphs and "g_head" in graph_state:
+                logits = graph_state["g_head"].static_outputs[0]
+            else:
+                logits = last_out["logits"]
+            _dump_outputs(args, {"tokens": graph_state["cur_id"] if use_graphs else cur,
+                                 "last_logits": logits})
         _emit_result(args, world, use_cuda, elapsed, B, "pipeline")
 
     if world > 1:
