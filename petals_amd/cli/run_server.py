@@ -63,6 +63,9 @@ def main(argv=None):
     parser.add_argument("--device", type=str, default=None)
     parser.add_argument("--torch_dtype", type=str, default="auto")
     parser.add_argument("--quant_type", type=str, default="none", choices=["none", "nf4", "int8"])
+    parser.add_argument("--prefill_gemm", type=str, default="dense", choices=["dense", "fused"],
+                        help="prefill matmuls on quantized weights: rocBLAS on cached dequantized "
+                             "copies (dense) or the dequant-fused MFMA GEMM (fused)")
     parser.add_argument("--attn_cache_tokens", type=int, default=16384)
     parser.add_argument("--max_batch_size", type=int, default=8)
     parser.add_argument("--max_chunk_size_bytes", type=int, default=256 * 1024 * 1024,
@@ -142,6 +145,12 @@ def main(argv=None):
 
         _os.environ["PETALS_AMD_CACHE"] = args.cache_dir
 
+    if args.prefill_gemm != "dense":
+        # process-wide, and set before the TP branch so shard ranks follow it
+        from petals_amd.ops.fused_decode import set_prefill_gemm_mode
+
+        set_prefill_gemm_mode(args.prefill_gemm)
+
     if args.tensor_parallel_ranks > 1:
         # launched under torchrun, one process per GPU: rank 0 is the swarm
         # Server; ranks 1.. execute their block shards in lockstep
@@ -215,6 +224,7 @@ def main(argv=None):
         cache_dir=args.cache_dir,
         max_disk_space=_parse_size(args.max_disk_space),
         tensor_parallel_ranks=args.tensor_parallel_ranks,
+        prefill_gemm=args.prefill_gemm,
     )
     server.start()
     print(f"petals_amd server listening on {server.listen_addr} peer_id={server.peer_id}", flush=True)

@@ -55,6 +55,10 @@ torch::Tensor moe_gemm(
     c10::optional<torch::Tensor> wt_all, c10::optional<torch::Tensor> packed_all,
     c10::optional<torch::Tensor> absmax_all, torch::Tensor x, torch::Tensor sorted_pairs,
     torch::Tensor tile_expert, int64_t k_per_tok, int64_t n_rows);
+torch::Tensor gemm_nf4(
+    torch::Tensor packed, torch::Tensor absmax, torch::Tensor x, c10::optional<torch::Tensor> bias);
+torch::Tensor gemm_int8(
+    torch::Tensor q8, torch::Tensor scale8, torch::Tensor x, c10::optional<torch::Tensor> bias);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rms_norm", &rms_norm, "RMSNorm (bf16 -> bf16)");
@@ -106,4 +110,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "into the LDS B-tile staging)",
         py::arg("wt_all"), py::arg("packed_all"), py::arg("absmax_all"), py::arg("x"),
         py::arg("sorted_pairs"), py::arg("tile_expert"), py::arg("k_per_tok"), py::arg("n_rows"));
+  m.def("gemm_nf4", &gemm_nf4,
+        "dense prefill MFMA GEMM x[M,in] @ NF4 W[in,out] (+bias) -> bf16, dequant fused into the "
+        "LDS staging",
+        py::arg("packed"), py::arg("absmax"), py::arg("x"), py::arg("bias") = py::none());
+  m.def("gemm_int8", &gemm_int8,
+        "dense prefill MFMA GEMM x[M,in] @ int8 W[in,out] (+bias) -> bf16, column scale in the "
+        "epilogue",
+        py::arg("q8"), py::arg("scale8"), py::arg("x"), py::arg("bias") = py::none());
 }

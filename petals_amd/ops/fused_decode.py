@@ -13,7 +13,8 @@ layout (transposed [in, out] bf16, QKV and gate/up concatenated) and then runs:
   prefill (q_len > 1): bf16 GEMMs via torch.matmul on the SAME transposed
     weights (rocBLAS), HIP rms_norm / rope / swiglu kernels, fp32-softmax
     attention (chunked by the backend; flash prefill kernel is the planned
-    upgrade).
+    upgrade). Opt-in PETALS_AMD_PREFILL_GEMM=fused: quantized weights run
+    these matmuls in the dequant-fused MFMA GEMM instead (_FastWeight.matmul).
 
 The original nn.Linear weights are FREED after repacking (a 70B span must not
 hold two copies).
@@ -83,6 +84,49 @@ class DecodeContext:
 
 
 _split_autotune_cache: Dict[Tuple[str, int, int], int] = {}
+
+_PREFILL_GEMM_MODES = ("dense", "fused")
+
+
+def prefill_gemm_mode() -> str:
+    """How quantized weights run their prefill matmuls, read at call time from
+    PETALS_AMD_PREFILL_GEMM: `dense` (default) is torch.matmul on the LRU-cached
+    dequantized copy; `fused` is the dequant-in-LDS MFMA GEMM (gemm_quant.hip),
+    which never materialises the bf16 weight."""
+    mode = os.environ.get("PETALS_AMD_PREFILL_GEMM", "dense")
+    if mode not in _PREFILL_GEMM_MODES:
+        raise ValueError(
+            f"PETALS_AMD_PREFILL_GEMM={mode!r}: expected one of {', '.join(_PREFILL_GEMM_MODES)}"
+        )
+    return mode
+
+
+def set_prefill_gemm_mode(mode: str) -> None:
+    """Process-wide setter behind Server(prefill_gemm=...) / --prefill_gemm."""
+    if mode not in _PREFILL_GEMM_MODES:
+        raise ValueError(f"prefill_gemm={mode!r}: expected one of {', '.join(_PREFILL_GEMM_MODES)}")
+    os.environ["PETALS_AMD_PREFILL_GEMM"] = mode
+
+
+# Largest row count the `fused` mode sends to the fused kernel, per format:
+# the measured crossover against dequantize + rocBLAS over the llama-2-70b
+# projection shapes (profiles/prefill_gemm_fused.log: NF4 wins everywhere at
+# 256 rows and loses at 512; int8, whose dequant is three torch passes, still
+# wins at 512 and loses at 2048). Larger chunks stay on dense() in any mode.
+FUSED_GEMM_MAX_ROWS = {"nf4": 256, "int8": 512}
+
+
+def fused_gemm_eligible(quant: str, rows: int, in_dim: int, out_dim: int) -> bool:
+    """Shapes the `fused` mode sends to the fused prefill GEMM: a quantized
+    weight whose in and out are multiples of 64 (the kernel's k step and the
+    NF4 block) and 1..FUSED_GEMM_MAX_ROWS[quant] rows (the kernel itself takes
+    any row count; past the crossover it loses to dequantize + rocBLAS)."""
+    return (
+        quant in FUSED_GEMM_MAX_ROWS
+        and 1 <= rows <= FUSED_GEMM_MAX_ROWS[quant]
+        and in_dim % 64 == 0
+        and out_dim % 64 == 0
+    )
 
 
 class _FastWeight:
@@ -182,6 +226,27 @@ class _FastWeight:
             )
         return self.t
 
+    def matmul(self, x: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x[..., in] @ W (+ bias) for inference-time prefill. In `fused` mode
+        an eligible quantized weight runs the dequant-fused MFMA GEMM on its
+        packed form (bias in the kernel epilogue); everything else is
+        torch.matmul on dense()."""
+        if (
+            prefill_gemm_mode() == "fused"
+            and not (torch.is_grad_enabled() and x.requires_grad)
+            and x.is_cuda
+            and x.dtype == torch.bfloat16
+            and fused_gemm_eligible(self.quant, x.numel() // max(x.shape[-1], 1), self.in_dim, self.out_dim)
+        ):
+            x2 = x.reshape(-1, self.in_dim).contiguous()
+            if self.quant == "nf4":
+                out = self.hip.gemm_nf4(self.packed, self.absmax, x2, bias)
+            else:
+                out = self.hip.gemm_int8(self.q8, self.scale8, x2, bias)
+            return out.view(*x.shape[:-1], self.out_dim)
+        out = torch.matmul(x, self.dense())
+        return out if bias is None else out + bias
+
 
 # ---- dequantized-weight LRU (keyed by _FastWeight identity, byte-bounded)
 _dequant_cache: "OrderedDict[int, torch.Tensor]" = None  # type: ignore[assignment]
@@ -263,6 +328,12 @@ class _TPFastPathMixin:
 
     tp_world = 1
     tp_group = None
+
+    @staticmethod
+    def _mm_autograd(w: "_FastWeight", x: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Differentiable matmul: always torch on the dense weight."""
+        out = torch.matmul(x, w.dense())
+        return out if bias is None else out + bias
 
     def _tp_copy(self, x: torch.Tensor) -> torch.Tensor:
         """Column-parallel input boundary (identity fwd, grad all-reduce bwd)."""
@@ -400,7 +471,10 @@ class LlamaFastPath(_TPFastPathMixin):
         (folded-norm weights take the scale-only normed x)."""
         xn2 = self._tp_copy(xn2)
         xd = xn2 if x_delta is None else x_delta
-        gateup = torch.matmul(xn2, self.wgateup_t.dense())
+        if autograd:
+            gateup = torch.matmul(xn2, self.wgateup_t.dense())
+        else:
+            gateup = self.wgateup_t.matmul(xn2)
         inter = self.wgateup_t.shape[1] // 2
         gate, up = gateup[..., :inter], gateup[..., inter:]
         if adapter is not None:
@@ -411,9 +485,10 @@ class LlamaFastPath(_TPFastPathMixin):
                 up = up + du
         if autograd:
             act = reference.swiglu(gate, up).to(xn2.dtype)
+            down = torch.matmul(act, self.wdown_t.dense())
         else:
             act = self.hip.swiglu(gate.contiguous(), up.contiguous())
-        down = torch.matmul(act, self.wdown_t.dense())
+            down = self.wdown_t.matmul(act)
         if adapter is not None:
             dd = adapter.delta("down", act)
             if dd is not None:
@@ -616,7 +691,7 @@ class LlamaFastPath(_TPFastPathMixin):
         self._ensure_rope(end)
 
         xn = self.hip.rms_norm(hidden, self.ln1_w_post, self.eps)
-        qkv = torch.matmul(xn, self.wqkv_t.dense())  # [B, S, qkv] bf16 (rocBLAS)
+        qkv = self.wqkv_t.matmul(xn)  # [B, S, qkv] bf16 (rocBLAS, or the fused GEMM)
         if adapter is not None:
             xd = self.hip.rms_norm(hidden, self.ln1_w, self.eps) if self.fold_norm else xn
             qkv = qkv + self._qkv_adapter_delta(xd, adapter).to(qkv.dtype)
@@ -638,7 +713,7 @@ class LlamaFastPath(_TPFastPathMixin):
                 q.contiguous(), k.contiguous(), v.contiguous(), S, 0, self.scale, True
             )
         attn = attn.transpose(1, 2).reshape(B, S, self.qh * self.hd).to(torch.bfloat16)
-        o = self._tp_reduce(torch.matmul(attn, self.wo_t.dense()))
+        o = self._tp_reduce(self.wo_t.matmul(attn))
         if adapter is not None:
             d = adapter.delta("o", attn)
             if d is not None:
@@ -836,7 +911,8 @@ class BloomFastPath(_TPFastPathMixin):
         xn = ln(hidden, self.ln1_w, self.ln1_b)
         res1 = xn if self.post_ln_residual else hidden
         xn = self._tp_copy(xn)
-        qkv = torch.matmul(xn, self.wqkv_t.dense()) + self.qkv_bias
+        mm = self._mm_autograd if autograd else _FastWeight.matmul  # inference: mode-selected
+        qkv = mm(self.wqkv_t, xn, self.qkv_bias)
         if adapter is not None:
             d = adapter.delta("qkv", xn)
             if d is not None:
@@ -860,7 +936,7 @@ class BloomFastPath(_TPFastPathMixin):
             attn = reference.attention(q.float(), k.float(), v.float(), causal=True,
                                        kv_offset=prefix_length, attn_bias=bias.float())
         attn = attn.transpose(1, 2).reshape(B, S, self.qh * self.hd).to(torch.bfloat16)
-        o = torch.matmul(attn, self.wo_t.dense()) + self.o_bias
+        o = mm(self.wo_t, attn, self.o_bias)
         if adapter is not None:
             d = adapter.delta("dense", attn)
             if d is not None:
@@ -869,13 +945,13 @@ class BloomFastPath(_TPFastPathMixin):
         xn2 = ln(h2, self.ln2_w, self.ln2_b)
         res2 = xn2 if self.post_ln_residual else h2
         xn2 = self._tp_copy(xn2)
-        inter = torch.matmul(xn2, self.w_h4h.dense()) + self.b_h4h
+        inter = mm(self.w_h4h, xn2, self.b_h4h)
         if adapter is not None:
             dh = adapter.delta("h4h", xn2)
             if dh is not None:
                 inter = inter + dh.to(inter.dtype)
         act = reference.gelu(inter.float()).to(torch.bfloat16)
-        out = torch.matmul(act, self.w_4hh.dense()) + self.b_4hh
+        out = mm(self.w_4hh, act, self.b_4hh)
         if adapter is not None:
             d4 = adapter.delta("4hh", act)
             if d4 is not None:
@@ -1074,7 +1150,8 @@ class FalconFastPath(_TPFastPathMixin):
 
         xn_attn = self._tp_copy(ln(hidden, self.ln_attn_w, self.ln_attn_b))
         xn_mlp = xn_attn if self.single_ln else self._tp_copy(ln(hidden, self.ln_mlp_w, self.ln_mlp_b))
-        qkv = torch.matmul(xn_attn, self.wqkv_t.dense())
+        mm = self._mm_autograd if autograd else _FastWeight.matmul  # inference: mode-selected
+        qkv = mm(self.wqkv_t, xn_attn)
         if adapter is not None:
             d = adapter.delta("qkv", xn_attn)
             if d is not None:
@@ -1100,8 +1177,8 @@ class FalconFastPath(_TPFastPathMixin):
                     q.contiguous(), k.contiguous(), v.contiguous(), S, 0, self.scale, True
                 )
         attn = attn.transpose(1, 2).reshape(B, S, self.qh * self.hd).to(torch.bfloat16)
-        o = torch.matmul(attn, self.wo_t.dense())
-        inter = torch.matmul(xn_mlp, self.w_h4h.dense())
+        o = mm(self.wo_t, attn)
+        inter = mm(self.w_h4h, xn_mlp)
         if adapter is not None:
             d = adapter.delta("dense", attn)
             if d is not None:
@@ -1110,7 +1187,7 @@ class FalconFastPath(_TPFastPathMixin):
             if dh is not None:
                 inter = inter + dh.to(inter.dtype)
         act = reference.gelu(inter.float()).to(torch.bfloat16)
-        mlp_out = torch.matmul(act, self.w_4hh.dense())
+        mlp_out = mm(self.w_4hh, act)
         if adapter is not None:
             d4 = adapter.delta("4hh", act)
             if d4 is not None:

@@ -84,6 +84,7 @@ class Server:
         max_disk_space: Optional[int] = None,
         tensor_parallel_ranks: int = 1,
         tp_group=None,
+        prefill_gemm: str = "dense",
     ):
         self.config = load_model_config(model_name_or_dir)
         self.model_name_or_dir = model_name_or_dir
@@ -163,6 +164,16 @@ class Server:
         # of `tensor_parallel_ranks` ranks sharding every served block
         self.tensor_parallel_ranks = int(tensor_parallel_ranks)
         self.tp_group = tp_group
+        # prefill matmuls on quantized weights: "fused" opts this PROCESS into
+        # the dequant-fused MFMA GEMM (ops/csrc/gemm_quant.hip); "dense" leaves
+        # the process setting (PETALS_AMD_PREFILL_GEMM, default dense) alone
+        from petals_amd.ops.fused_decode import _PREFILL_GEMM_MODES, set_prefill_gemm_mode
+
+        if prefill_gemm not in _PREFILL_GEMM_MODES:
+            raise ValueError(f"prefill_gemm={prefill_gemm!r}: expected one of {_PREFILL_GEMM_MODES}")
+        self.prefill_gemm = prefill_gemm
+        if prefill_gemm == "fused":
+            set_prefill_gemm_mode("fused")
 
     # -------------------------------------------------------------- sizing
 
