@@ -146,4 +146,10 @@ PRESETS = {
         max_position_embeddings=256, rms_norm_eps=1e-5, rope_theta=10000.0,
         num_local_experts=4, num_experts_per_tok=2,
     ),
+    "test-mixtral-hd64": dict(  # fused-path geometry (head_dim 64) for GPU serving tests
+        model_type="mixtral", hidden_size=256, num_hidden_layers=4, num_attention_heads=4,
+        num_key_value_heads=2, intermediate_size=512, vocab_size=128,
+        max_position_embeddings=256, rms_norm_eps=1e-5, rope_theta=10000.0,
+        num_local_experts=4, num_experts_per_tok=2,
+    ),
 }

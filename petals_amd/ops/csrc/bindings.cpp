@@ -54,7 +54,12 @@ torch::Tensor gemv_nf4_moe(
 torch::Tensor moe_gemm(
     c10::optional<torch::Tensor> wt_all, c10::optional<torch::Tensor> packed_all,
     c10::optional<torch::Tensor> absmax_all, torch::Tensor x, torch::Tensor sorted_pairs,
-    torch::Tensor tile_expert, int64_t k_per_tok, int64_t n_rows);
+    torch::Tensor tile_expert, int64_t k_per_tok, int64_t n_rows,
+    c10::optional<torch::Tensor> q8_all, c10::optional<torch::Tensor> scale8_all);
+torch::Tensor gemv_int8_moe(
+    torch::Tensor q8_all, torch::Tensor scale8_all, torch::Tensor x, torch::Tensor sel,
+    int64_t k_per_tok, torch::Tensor workspace, int64_t epilogue, int64_t splits_override);
+int64_t gemv_int8_moe_splits(int64_t in_dim, int64_t out_dim, int64_t rows, int64_t splits_override);
 torch::Tensor gemm_nf4(
     torch::Tensor packed, torch::Tensor absmax, torch::Tensor x, c10::optional<torch::Tensor> bias);
 torch::Tensor gemm_int8(
@@ -106,10 +111,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("packed_all"), py::arg("absmax_all"), py::arg("x"), py::arg("sel"),
         py::arg("k_per_tok"), py::arg("workspace"), py::arg("epilogue"), py::arg("splits") = 0);
   m.def("moe_gemm", &moe_gemm,
-        "grouped MFMA GEMM over expert-sorted (token, slot) pairs (prefill; NF4 dequant fused "
-        "into the LDS B-tile staging)",
+        "grouped MFMA GEMM over expert-sorted (token, slot) pairs (prefill; NF4/int8 dequant "
+        "fused into the LDS B-tile staging); exactly one of wt_all / packed_all / q8_all",
         py::arg("wt_all"), py::arg("packed_all"), py::arg("absmax_all"), py::arg("x"),
-        py::arg("sorted_pairs"), py::arg("tile_expert"), py::arg("k_per_tok"), py::arg("n_rows"));
+        py::arg("sorted_pairs"), py::arg("tile_expert"), py::arg("k_per_tok"), py::arg("n_rows"),
+        py::arg("q8_all") = py::none(), py::arg("scale8_all") = py::none());
+  m.def("gemv_int8_moe", &gemv_int8_moe,
+        "device-routed MoE gemv: stacked int8 expert weights (per-column scales), expert ids "
+        "from a device tensor",
+        py::arg("q8_all"), py::arg("scale8_all"), py::arg("x"), py::arg("sel"),
+        py::arg("k_per_tok"), py::arg("workspace"), py::arg("epilogue"), py::arg("splits") = 0);
+  m.def("gemv_int8_moe_splits", &gemv_int8_moe_splits,
+        "split count gemv_int8_moe uses for (in, out, rows) — sizes the workspace",
+        py::arg("in_dim"), py::arg("out_dim"), py::arg("rows"), py::arg("splits") = 0);
   m.def("gemm_nf4", &gemm_nf4,
         "dense prefill MFMA GEMM x[M,in] @ NF4 W[in,out] (+bias) -> bf16, dequant fused into the "
         "LDS staging",

@@ -271,7 +271,7 @@ __global__ void swiglu_kernel(
     const unsigned short* __restrict__ up,
     unsigned short* __restrict__ y,
     long n) {
-  const long i = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
+  const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
   if (i + 8 <= n) {
     const short8 g8 = *reinterpret_cast<const short8*>(gate + i);
     const short8 u8 = *reinterpret_cast<const short8*>(up + i);
@@ -297,7 +297,11 @@ torch::Tensor swiglu(torch::Tensor gate, torch::Tensor up) {
   auto g = gate.contiguous(), u = up.contiguous();
   auto y = torch::empty_like(g);
   const long n = g.numel();
-  const long blocks = std::min((n / 8 + 255) / 256 + 1, (long)4096);
+  // one 8-element chunk per thread and no grid-stride loop: the grid must
+  // cover all of n (a 4096-block cap left everything past 8M elements
+  // unwritten, which a long grouped MoE prefill reaches)
+  const long blocks = (n / 8 + 255) / 256 + 1;
+  TORCH_CHECK(blocks < (1L << 31), "swiglu: too many elements");
   auto stream = at::cuda::getCurrentCUDAStream();
   swiglu_kernel<<<blocks, 256, 0, stream>>>(
       reinterpret_cast<const unsigned short*>(g.data_ptr()),

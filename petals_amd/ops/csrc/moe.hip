@@ -12,6 +12,7 @@
 // expert axis:
 //   bf16: wt_all   [E, in, out]
 //   nf4:  packed   [E, in, out/2], absmax [E, in, out/64]
+//   int8: q8_all   [E, in, out] s8,  scale8 [E, out] bf16 (per out column)
 // The per-row inner loop is the same x-broadcast split-K structure as the
 // dense kernels (each selected expert's weights are read exactly once per
 // token).
@@ -220,6 +221,80 @@ __global__ __launch_bounds__(WAVE) void gemv_nf4_moe_kernel(
   }
 }
 
+// ------------------------------------------------------------ int8 indexed
+//
+// The inner loop, the scale fold and the partial layout are int8.hip's
+// gemv_int8_kernel<1> (16 char8 loads in flight, fmaf in ascending i, tail
+// rows, scale once per partial write), so virtual row r is bit-identical to
+// gemv_int8(q8_all[e], scale8_all[e], x[r / k]) at the same split count.
+// The host requires out % 8 == 0 (the 8-byte loads need it), so a lane is
+// either fully live or returns: no per-element edge branch.
+
+using char8_moe = __attribute__((ext_vector_type(8))) char;
+
+__global__ __launch_bounds__(WAVE) void gemv_int8_moe_kernel(
+    const signed char* __restrict__ q8_all,         // [E, in, out]
+    const unsigned short* __restrict__ scale8_all,  // [E, out] bf16
+    const float* __restrict__ x,                    // [B, in]
+    const int* __restrict__ sel,                    // [R] expert per virtual row
+    float* __restrict__ partials,                   // [n_splits, R, out]
+    int in_dim,
+    int out_dim,
+    int i_per_split,
+    int rows,
+    int k_per_tok) {
+  const int row = blockIdx.z;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int out0 = blockIdx.x * GEMV_OUT_PER_WAVE + lane * 8;
+  if (out0 >= out_dim) return;  // out % 8 == 0: a live lane owns 8 full columns
+  const int split = blockIdx.y;
+  const int i_begin = split * i_per_split;
+  const int i_end = min(i_begin + i_per_split, in_dim);
+
+  const int e = sel[row];
+  const signed char* q = q8_all + (size_t)e * in_dim * out_dim;
+  const unsigned short* scale = scale8_all + (size_t)e * out_dim;
+  const float* xr = x + (size_t)(row / k_per_tok) * in_dim;
+
+  float acc[8];
+#pragma unroll
+  for (int v = 0; v < 8; ++v) acc[v] = 0.f;
+
+  constexpr int UNROLL = 16;  // 128 B of weight loads in flight per lane
+  int i = i_begin;
+  const signed char* wp = q + (size_t)i_begin * out_dim + out0;
+  for (; i + UNROLL <= i_end; i += UNROLL) {
+    char8_moe w8[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+      w8[u] = *reinterpret_cast<const char8_moe*>(wp + (size_t)u * out_dim);
+    float xs[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) xs[u] = xr[i + u];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+#pragma unroll
+      for (int v = 0; v < 8; ++v) acc[v] = fmaf((float)w8[u][v], xs[u], acc[v]);
+    }
+    wp += (size_t)UNROLL * out_dim;
+  }
+  for (; i < i_end; ++i) {
+    const char8_moe w8 = *reinterpret_cast<const char8_moe*>(q + (size_t)i * out_dim + out0);
+    const float xv = xr[i];
+#pragma unroll
+    for (int v = 0; v < 8; ++v) acc[v] = fmaf((float)w8[v], xv, acc[v]);
+  }
+
+  // fold the expert's per-column scale into the partial write (once per split)
+  const short8 sc8 = *reinterpret_cast<const short8*>(scale + out0);
+  float sc[8];
+#pragma unroll
+  for (int v = 0; v < 8; ++v) sc[v] = bf16_to_f32((unsigned short)sc8[v]);
+  float4v* d4 = reinterpret_cast<float4v*>(partials + ((size_t)split * rows + row) * out_dim + out0);
+  d4[0] = float4v{acc[0] * sc[0], acc[1] * sc[1], acc[2] * sc[2], acc[3] * sc[3]};
+  d4[1] = float4v{acc[4] * sc[4], acc[5] * sc[5], acc[6] * sc[6], acc[7] * sc[7]};
+}
+
 // ------------------------------------------------- grouped GEMM (prefill)
 //
 // Prefill-time grouped GEMM over expert-sorted (token, slot) pairs: the host
@@ -242,11 +317,19 @@ __global__ __launch_bounds__(WAVE) void gemv_nf4_moe_kernel(
 #define BT_BYTE(n, k_byte) \
   ((((unsigned)(n)) * ((MOE_KT + MOE_KPAD) * 2) + (unsigned)(k_byte)) ^ ((((unsigned)(n) >> 3) & 7u) << 4))
 
-template <bool NF4>
+enum MoeWeightMode : int { MOE_W_BF16 = 0, MOE_W_NF4 = 1, MOE_W_INT8 = 2 };
+
+// s8 -> bf16 bits (exact: |v| <= 127 needs 7 significand bits)
+__device__ __forceinline__ unsigned short moe_s8_bf16(unsigned int word, int byte) {
+  const int v = (int)(word << (24 - 8 * byte)) >> 24;
+  return (unsigned short)(__float_as_uint((float)v) >> 16);
+}
+
+template <int MODE>
 __global__ __launch_bounds__(256) void moe_gemm_kernel(
-    const unsigned short* __restrict__ wt_all,      // [E, in, out] bf16 (NF4: null)
-    const unsigned char* __restrict__ packed_all,   // [E, in, out/2] u8 (bf16: null)
-    const unsigned short* __restrict__ absmax_all,  // [E, in, out/64] bf16 (bf16: null)
+    const unsigned short* __restrict__ wt_all,      // [E, in, out] bf16 (else null)
+    const unsigned char* __restrict__ packed_all,   // nf4: [E, in, out/2] u8; int8: q8 [E, in, out] s8
+    const unsigned short* __restrict__ absmax_all,  // nf4: [E, in, out/64] bf16; int8: scale8 [E, out] bf16
     const unsigned short* __restrict__ x,           // [T, in] bf16
     const int* __restrict__ sorted_pairs,           // [Rp] pair id or -1 (padding)
     const int* __restrict__ tile_expert,            // [Rp/MT] expert id or -1
@@ -265,6 +348,7 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
   const int col = lane & 15;
   const int hi = lane >> 4;
 
+  constexpr bool NF4 = MODE == MOE_W_NF4;
   __shared__ float2 lut2[256];
   if (NF4) {
     for (int i = tid; i < 256; i += 256)
@@ -319,6 +403,23 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
             *reinterpret_cast<unsigned short*>(&bt_raw[BT_BYTE(n, kb)]) = f32_to_bf16(w2.x * am);
             *reinterpret_cast<unsigned short*>(&bt_raw[BT_BYTE(n + 1, kb)]) = f32_to_bf16(w2.y * am);
           }
+      } else if (MODE == MOE_W_INT8) {
+        // 32 s8 columns of one k row = two 16-byte loads; staged as bf16 (exact)
+        const int kb = (krow - kt) * 2;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          uint4 p = make_uint4(0u, 0u, 0u, 0u);
+          if (krow < in_dim && n0 + nloc + h * 16 < out_dim)
+            p = *reinterpret_cast<const uint4*>(
+                packed_all + (size_t)e * w_stride + (size_t)krow * out_dim + n0 + nloc + h * 16);
+          const unsigned int wd[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+          for (int w4 = 0; w4 < 4; ++w4)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+              *reinterpret_cast<unsigned short*>(&bt_raw[BT_BYTE(nloc + h * 16 + w4 * 4 + b, kb)]) =
+                  moe_s8_bf16(wd[w4], b);
+        }
       } else {
         const int kb = (krow - kt) * 2;
 #pragma unroll
@@ -366,6 +467,17 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
     }
   }
 
+  // int8: this lane's two column scales (n depends only on nb), applied to
+  // the fp32 accumulator before the single bf16 rounding
+  float csc[2] = {1.f, 1.f};
+  if (MODE == MOE_W_INT8) {
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+      const int n = n0 + wave * 32 + nb * 16 + col;
+      if (n < out_dim) csc[nb] = bf16_to_f32(absmax_all[(size_t)e * out_dim + n]);
+    }
+  }
+
   // ---- write C (bf16, original pair rows): C row = hi*4 + r within block
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb)
@@ -376,7 +488,10 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
         const int n = n0 + wave * 32 + nb * 16 + col;
-        if (n < out_dim) c[(size_t)pr * out_dim + n] = f32_to_bf16(acc[rb][nb][r]);
+        if (n >= out_dim) continue;
+        float val = acc[rb][nb][r];
+        if (MODE == MOE_W_INT8) val *= csc[nb];
+        c[(size_t)pr * out_dim + n] = f32_to_bf16(val);
       }
     }
 }
@@ -391,13 +506,29 @@ torch::Tensor moe_gemm(
     torch::Tensor sorted_pairs,               // [Rp] i32 (expert-sorted, MT-padded, -1 = pad)
     torch::Tensor tile_expert,                // [Rp/MT] i32 (-1 = pure padding tile)
     int64_t k_per_tok,
-    int64_t n_rows) {                         // R = T * k_per_tok (C rows)
+    int64_t n_rows,                           // R = T * k_per_tok (C rows)
+    c10::optional<torch::Tensor> q8_all,      // [E, in, out] s8
+    c10::optional<torch::Tensor> scale8_all) {  // [E, out] bf16
   TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.dim() == 2 && x.is_contiguous());
   TORCH_CHECK(sorted_pairs.dtype() == torch::kInt32 && sorted_pairs.is_contiguous());
   TORCH_CHECK(tile_expert.dtype() == torch::kInt32 && tile_expert.is_contiguous());
   const bool nf4 = packed_all.has_value();
+  const bool int8 = q8_all.has_value();
+  TORCH_CHECK((int)wt_all.has_value() + (int)nf4 + (int)int8 == 1,
+              "moe_gemm takes exactly one of wt_all, packed_all, q8_all");
   int in_dim, out_dim;
-  if (nf4) {
+  if (int8) {
+    TORCH_CHECK(q8_all->is_cuda() && q8_all->dtype() == torch::kInt8 && q8_all->dim() == 3 &&
+                q8_all->is_contiguous());
+    in_dim = q8_all->size(1);
+    out_dim = q8_all->size(2);
+    TORCH_CHECK(scale8_all.has_value() && scale8_all->is_cuda() &&
+                    scale8_all->dtype() == torch::kBFloat16 && scale8_all->dim() == 2 &&
+                    scale8_all->is_contiguous() && scale8_all->size(0) == q8_all->size(0) &&
+                    scale8_all->size(1) == out_dim,
+                "moe_gemm: scale8_all must be a contiguous bf16 [E, out]");
+    TORCH_CHECK(!absmax_all.has_value(), "moe_gemm: absmax_all goes with packed_all");
+  } else if (nf4) {
     TORCH_CHECK(packed_all->dtype() == torch::kUInt8 && packed_all->dim() == 3 && packed_all->is_contiguous());
     TORCH_CHECK(absmax_all.has_value() && absmax_all->dtype() == torch::kBFloat16);
     in_dim = packed_all->size(1);
@@ -418,15 +549,22 @@ torch::Tensor moe_gemm(
   auto c = torch::empty({n_rows, (long)out_dim}, x.options());
   dim3 grid(Rp / MOE_MT, (out_dim + MOE_NT - 1) / MOE_NT);
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (nf4) {
-    moe_gemm_kernel<true><<<grid, 256, 0, stream>>>(
+  if (int8) {
+    moe_gemm_kernel<MOE_W_INT8><<<grid, 256, 0, stream>>>(
+        nullptr, reinterpret_cast<const unsigned char*>(q8_all->data_ptr()),
+        reinterpret_cast<const unsigned short*>(scale8_all->data_ptr()),
+        reinterpret_cast<const unsigned short*>(x.data_ptr()),
+        sorted_pairs.data_ptr<int>(), tile_expert.data_ptr<int>(),
+        reinterpret_cast<unsigned short*>(c.data_ptr()), in_dim, out_dim, (int)k_per_tok);
+  } else if (nf4) {
+    moe_gemm_kernel<MOE_W_NF4><<<grid, 256, 0, stream>>>(
         nullptr, packed_all->data_ptr<unsigned char>(),
         reinterpret_cast<const unsigned short*>(absmax_all->data_ptr()),
         reinterpret_cast<const unsigned short*>(x.data_ptr()),
         sorted_pairs.data_ptr<int>(), tile_expert.data_ptr<int>(),
         reinterpret_cast<unsigned short*>(c.data_ptr()), in_dim, out_dim, (int)k_per_tok);
   } else {
-    moe_gemm_kernel<false><<<grid, 256, 0, stream>>>(
+    moe_gemm_kernel<MOE_W_BF16><<<grid, 256, 0, stream>>>(
         reinterpret_cast<const unsigned short*>(wt_all->data_ptr()), nullptr, nullptr,
         reinterpret_cast<const unsigned short*>(x.data_ptr()),
         sorted_pairs.data_ptr<int>(), tile_expert.data_ptr<int>(),
@@ -519,4 +657,78 @@ torch::Tensor gemv_nf4_moe(
   return launch_gemv_reduce(
       partials, c10::nullopt, c10::nullopt, (int)splits, rows, out_dim, (int)epilogue,
       x.options(), absmax_all.options());
+}
+
+// Split policy of gemv_int8_moe, exposed so the Python side can size the
+// shared gemv workspace for it before a span graph is captured.
+#define MOE_I8_SPLIT_TARGET 1024  // workgroups over out_waves * rows (docs/KERNELS.md: sweep + serve A/B)
+#define MOE_I8_MIN_CHUNK 128      // input rows per split, as gemv_int8
+
+int64_t gemv_int8_moe_splits(int64_t in_dim, int64_t out_dim, int64_t rows, int64_t splits_override) {
+  const long out_waves = (out_dim + GEMV_OUT_PER_WAVE - 1) / GEMV_OUT_PER_WAVE;
+  const long wgs = out_waves * (rows > 0 ? rows : 1);
+  // PETALS_AMD_MOE_INT8_SPLIT_TARGET selects another target for A/B runs
+  static const long target = [] {
+    const char* env = std::getenv("PETALS_AMD_MOE_INT8_SPLIT_TARGET");
+    const long t = env ? std::atol(env) : 0;
+    return t > 0 ? t : (long)MOE_I8_SPLIT_TARGET;
+  }();
+  long splits = splits_override > 0 ? splits_override : (target + wgs - 1) / wgs;
+  const long max_splits = (in_dim + MOE_I8_MIN_CHUNK - 1) / MOE_I8_MIN_CHUNK;
+  if (splits > max_splits) splits = max_splits;
+  if (splits < 1) splits = 1;
+  return splits;
+}
+
+torch::Tensor gemv_int8_moe(
+    torch::Tensor q8_all,      // [E, in, out] s8
+    torch::Tensor scale8_all,  // [E, out] bf16
+    torch::Tensor x,           // [B, in] f32
+    torch::Tensor sel,         // [R] int32 (R = B * k)
+    int64_t k_per_tok,
+    torch::Tensor workspace,
+    int64_t epilogue,
+    int64_t splits_override) {
+  TORCH_CHECK(q8_all.is_cuda() && q8_all.dtype() == torch::kInt8 && q8_all.dim() == 3 &&
+                  q8_all.is_contiguous(),
+              "gemv_int8_moe: q8_all must be a contiguous s8 [E, in, out] GPU tensor");
+  const int in_dim = q8_all.size(1), out_dim = q8_all.size(2);
+  TORCH_CHECK(scale8_all.is_cuda() && scale8_all.dtype() == torch::kBFloat16 &&
+                  scale8_all.dim() == 2 && scale8_all.is_contiguous() &&
+                  scale8_all.size(0) == q8_all.size(0) && scale8_all.size(1) == out_dim,
+              "gemv_int8_moe: scale8_all must be a contiguous bf16 [E, out] GPU tensor");
+  TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kFloat32 && x.dim() == 2 && x.is_contiguous(),
+              "gemv_int8_moe: x must be a contiguous f32 [B, in] GPU tensor");
+  TORCH_CHECK(sel.is_cuda() && sel.dtype() == torch::kInt32 && sel.dim() == 1 && sel.is_contiguous(),
+              "gemv_int8_moe: sel must be a contiguous int32 [R] GPU tensor");
+  TORCH_CHECK(workspace.is_cuda() && workspace.dtype() == torch::kFloat32 && workspace.is_contiguous());
+  TORCH_CHECK(k_per_tok >= 1);
+  const int rows = sel.size(0);
+  TORCH_CHECK(x.size(1) == in_dim && rows == x.size(0) * k_per_tok,
+              "gemv_int8_moe: need x [B, in] and sel of length B * k_per_tok");
+  TORCH_CHECK(rows >= 1 && rows <= 16, "moe gemv supports batch*k <= 16");
+  TORCH_CHECK(out_dim % 8 == 0, "gemv_int8_moe needs out_dim % 8 == 0 (8-byte weight loads)");
+  TORCH_CHECK(epilogue >= 0, "gemv_int8_moe has no raw-partials mode");
+
+  const long out_waves = (out_dim + GEMV_OUT_PER_WAVE - 1) / GEMV_OUT_PER_WAVE;
+  const long splits = gemv_int8_moe_splits(in_dim, out_dim, rows, splits_override);
+  const int i_per_split = (in_dim + (int)splits - 1) / (int)splits;
+
+  torch::Tensor partials;
+  if (workspace.numel() >= (int64_t)splits * rows * out_dim) {
+    partials = workspace;
+  } else {
+    partials = torch::empty({splits, (long)rows, (long)out_dim}, x.options());
+  }
+  dim3 grid(out_waves, splits, rows);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  gemv_int8_moe_kernel<<<grid, WAVE, 0, stream>>>(
+      reinterpret_cast<const signed char*>(q8_all.data_ptr()),
+      reinterpret_cast<const unsigned short*>(scale8_all.data_ptr()),
+      x.data_ptr<float>(), sel.data_ptr<int>(), partials.data_ptr<float>(),
+      in_dim, out_dim, i_per_split, rows, (int)k_per_tok);
+  HIP_CHECK_LAST();
+  return launch_gemv_reduce(
+      partials, c10::nullopt, c10::nullopt, (int)splits, rows, out_dim, (int)epilogue,
+      x.options(), scale8_all.options());
 }

@@ -5,18 +5,19 @@ Decode routing runs entirely ON the GPU (router gemm -> softmax -> top-k ->
 int32 expert ids in a device tensor) and the expert GEMVs read their expert's
 stacked weights through that tensor (ops/csrc/moe.hip), so there is no host
 sync per step and the whole span is hipGraph-capturable (graph_safe) for the
-bf16 and NF4 quantizations. Each selected expert's weights are read exactly
-once per token — the decode-time degenerate case of a grouped GEMM.
+bf16, NF4 and int8 quantizations. Each selected expert's weights are read
+exactly once per token — the decode-time degenerate case of a grouped GEMM.
 
 (The reference runs Mixtral experts densely inside one server's HF block with
 host-side routing: reference models/mixtral/block.py:73-81.)
 
-int8 expert weights keep the round-1 host-routed per-expert GEMV path
-(graph_safe = False).
+PETALS_AMD_MOE_INT8=host (read at block construction) keeps int8 experts on
+the older host-routed per-expert GEMV path (graph_safe = False) for A/B runs.
 """
 
 from __future__ import annotations
 
+import os
 from typing import List, Optional
 
 import torch
@@ -32,6 +33,15 @@ from petals_amd.ops.fused_decode import (
 
 
 MOE_GEMM_MT = 32  # moe_gemm C-tile rows (ops/csrc/moe.hip MOE_MT)
+
+
+def moe_int8_mode() -> str:
+    """'device' (default): stacked int8 experts, device-routed gemv_int8_moe /
+    grouped moe_gemm. 'host': one _FastWeight per expert, host-synced routing."""
+    mode = os.environ.get("PETALS_AMD_MOE_INT8", "device").lower()
+    if mode not in ("device", "host"):
+        raise ValueError(f"PETALS_AMD_MOE_INT8 must be 'device' or 'host', got {mode!r}")
+    return mode
 
 
 def sort_pairs_by_expert(selected: torch.Tensor, num_experts: int):
@@ -81,6 +91,17 @@ class _StackedExperts:
                 absmax.append(a)
             self.packed_all = torch.stack(packed).contiguous()
             self.absmax_all = torch.stack(absmax).contiguous()
+        elif quant == "int8":
+            # per expert exactly as _FastWeight: per-out-column absmax / 127
+            # (plain torch, so this form also constructs on the CPU with hip=None)
+            q8, scale8 = [], []
+            for t in t_list:
+                w = t.float()
+                scale = w.abs().amax(dim=0).clamp_min(1e-8) / 127.0
+                q8.append(torch.round(w / scale).clamp(-127, 127).to(torch.int8))
+                scale8.append(scale.to(torch.bfloat16))
+            self.q8_all = torch.stack(q8).contiguous()        # [E, in, out] s8
+            self.scale8_all = torch.stack(scale8).contiguous()  # [E, out] bf16
         else:
             assert quant == "none"
             self.wt_all = torch.stack([t.contiguous() for t in t_list]).contiguous()
@@ -92,6 +113,8 @@ class _StackedExperts:
                  epilogue: int) -> torch.Tensor:
         if self.quant == "nf4":
             return self.hip.gemv_nf4_moe(self.packed_all, self.absmax_all, x, sel, k_per_tok, ws, epilogue)
+        if self.quant == "int8":
+            return self.hip.gemv_int8_moe(self.q8_all, self.scale8_all, x, sel, k_per_tok, ws, epilogue)
         return self.hip.gemv_bf16_moe(self.wt_all, x, sel, k_per_tok, ws, epilogue)
 
     def moe_gemm(self, x: torch.Tensor, sorted_pairs: torch.Tensor, tile_expert: torch.Tensor,
@@ -100,8 +123,19 @@ class _StackedExperts:
         if self.quant == "nf4":
             return self.hip.moe_gemm(None, self.packed_all, self.absmax_all, x,
                                      sorted_pairs, tile_expert, k_per_tok, n_rows)
+        if self.quant == "int8":
+            return self.hip.moe_gemm(None, None, None, x, sorted_pairs, tile_expert, k_per_tok, n_rows,
+                                     self.q8_all, self.scale8_all)
         return self.hip.moe_gemm(self.wt_all, None, None, x, sorted_pairs, tile_expert,
                                  k_per_tok, n_rows)
+
+    def gemv_ws_floats(self, rows: int) -> int:
+        """f32 workspace elements moe_gemv needs for `rows` virtual rows under
+        the kernel's default split policy (0 = not reported for this quant:
+        the bf16/NF4 kernels' needs are covered by the shared 64*B*out rule)."""
+        if self.quant != "int8":
+            return 0
+        return self.hip.gemv_int8_moe_splits(self.in_dim, self.out_dim, rows) * rows * self.out_dim
 
     @property
     def gemm_ok(self) -> bool:
@@ -114,6 +148,11 @@ class _StackedExperts:
             return _dequant_cached(
                 self._cache_keys[e],
                 lambda: self.hip.nf4_dequantize(self.packed_all[e], self.absmax_all[e]),
+            )
+        if self.quant == "int8":
+            return _dequant_cached(
+                self._cache_keys[e],
+                lambda: (self.q8_all[e].to(torch.float32) * self.scale8_all[e].float()).to(torch.bfloat16),
             )
         return self.wt_all[e]
 
@@ -135,7 +174,7 @@ class MixtralFastPath(LlamaFastPath):
         self.stacked_down: Optional[_StackedExperts] = None
         self.wgateup_e: List[_FastWeight] = []
         self.wdown_e: List[_FastWeight] = []
-        if quant in ("none", "nf4"):
+        if quant in ("none", "nf4") or (quant == "int8" and moe_int8_mode() == "device"):
             gu_list = [torch.cat([t(e.w1.weight), t(e.w3.weight)], dim=1) for e in moe.experts]
             down_list = [t(e.w2.weight) for e in moe.experts]
             self.stacked_gu = _StackedExperts(gu_list, hip_ops, quant)
@@ -147,15 +186,31 @@ class MixtralFastPath(LlamaFastPath):
                     _FastWeight(torch.cat([t(expert.w1.weight), t(expert.w3.weight)], dim=1), hip_ops, quant)
                 )
                 self.wdown_e.append(_FastWeight(t(expert.w2.weight), hip_ops, quant))
-            self.graph_safe = False  # host-routed fallback
+            self.graph_safe = False  # host-routed (PETALS_AMD_MOE_INT8=host)
         for expert in moe.experts:
             for lin in (expert.w1, expert.w2, expert.w3):
                 lin.weight.data = self._empty_bf16
         moe.gate.weight.data = self._empty_bf16
 
     def _max_gemv_out(self) -> int:
+        # called on every decode step; depends only on construction-time shapes
+        cached = getattr(self, "_max_gemv_out_cached", None)
+        if cached is None:
+            cached = self._max_gemv_out_cached = self._compute_max_gemv_out()
+        return cached
+
+    def _compute_max_gemv_out(self) -> int:
         gu_out = self.stacked_gu.out_dim if self.stacked_gu is not None else self.wgateup_e[0].shape[1]
-        return max(gu_out, self.wqkv_t.shape[1], self.wo_t.shape[1])
+        out = max(gu_out, self.wqkv_t.shape[1], self.wo_t.shape[1])
+        if self.stacked_gu is not None:
+            # the decode workspace is 64 * B * this value: make sure it holds the
+            # routed gemvs' splits * (B * top_k) * out partials at every decode
+            # batch, so a captured span graph never sees the workspace grow
+            for st in (self.stacked_gu, self.stacked_down):
+                for b in range(1, 16 // self.top_k + 1):
+                    need = st.gemv_ws_floats(b * self.top_k)
+                    out = max(out, -(-need // (64 * b)))
+        return out
 
     def _route(self, xn2: torch.Tensor):
         """Router on [tokens, H] f32/bf16 -> (weights [t, k], experts [t, k]).
@@ -198,10 +253,12 @@ class MixtralFastPath(LlamaFastPath):
 
     def _mlp_dense(self, xn2, adapter, autograd: bool, x_delta=None):
         """Prefill / training MLP over the routed experts. Inference prefill
-        runs the grouped MFMA GEMM (ops/csrc/moe.hip moe_gemm: NF4 dequant
-        fused into the LDS B-tile staging — packed weights are what cross
-        HBM, read ceil(rows_e/32) times per expert instead of once per
-        token); training/CPU fall back to token-grouped dense matmuls."""
+        runs the grouped MFMA GEMM (ops/csrc/moe.hip moe_gemm: NF4 / int8
+        dequant fused into the LDS B-tile staging — packed weights are what
+        cross HBM, read ceil(rows_e/32) times per expert instead of once per
+        token); training/CPU fall back to token-grouped dense matmuls.
+        int8 routes grouped at every T: it beat the dense loop on a dequant
+        LRU miss at every measured row count (docs/KERNELS.md)."""
         shape = xn2.shape
         x = xn2.reshape(-1, shape[-1])
         weights, selected = self._route(x)
