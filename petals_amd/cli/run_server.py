@@ -62,7 +62,7 @@ def main(argv=None):
     parser.add_argument("--dht_prefix", type=str, default=None)
     parser.add_argument("--device", type=str, default=None)
     parser.add_argument("--torch_dtype", type=str, default="auto")
-    parser.add_argument("--quant_type", type=str, default="none", choices=["none", "nf4", "int8"])
+    parser.add_argument("--quant_type", type=str, default="none", choices=["none", "nf4", "int8", "mxfp4"])
     parser.add_argument("--prefill_gemm", type=str, default="dense", choices=["dense", "fused"],
                         help="prefill matmuls on quantized weights: rocBLAS on cached dequantized "
                              "copies (dense) or the dequant-fused MFMA GEMM (fused)")

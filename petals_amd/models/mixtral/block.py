@@ -65,6 +65,11 @@ class MixtralBlock(nn.Module):
 
     def optimize_for_inference(self, quant: str = "none") -> "MixtralBlock":
         """MI355X fast path: fused attention decode + routed expert GEMVs."""
+        if quant == "mxfp4":
+            raise NotImplementedError(
+                "Mixtral has no MXFP4 path yet: the stacked expert kernels (gemv_*_moe, moe_gemm) "
+                "take bf16, nf4 and int8 experts only; serve it with quant_type none, nf4 or int8"
+            )
         from petals_amd import ops as _ops
         from petals_amd.ops.fused_moe import MixtralFastPath
 

@@ -16,7 +16,7 @@ BUILD_DIR = os.path.join(PKG_DIR, "_build")
 SO_PATH = os.path.join(PKG_DIR, "_hip_ops.so")
 
 SOURCES = ["bindings.cpp", "elementwise.hip", "gemv.hip", "attention.hip", "nf4.hip", "int8.hip", "prefill_attn.hip", "moe.hip",
-           "gemm_quant.hip"]
+           "gemm_quant.hip", "mxfp4.hip"]
 
 
 def build(verbose: bool = False) -> str:

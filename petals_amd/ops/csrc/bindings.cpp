@@ -64,6 +64,15 @@ torch::Tensor gemm_nf4(
     torch::Tensor packed, torch::Tensor absmax, torch::Tensor x, c10::optional<torch::Tensor> bias);
 torch::Tensor gemm_int8(
     torch::Tensor q8, torch::Tensor scale8, torch::Tensor x, c10::optional<torch::Tensor> bias);
+std::vector<torch::Tensor> mxfp4_quantize(torch::Tensor w);
+torch::Tensor mxfp4_dequantize(torch::Tensor packed, torch::Tensor scales);
+torch::Tensor gemv_mxfp4(
+    torch::Tensor packed, torch::Tensor scales, torch::Tensor x, torch::Tensor workspace,
+    c10::optional<torch::Tensor> residual, int64_t epilogue, int64_t splits_override,
+    c10::optional<torch::Tensor> bias);
+int64_t gemv_mxfp4_splits(int64_t in_dim, int64_t out_dim, int64_t batch, int64_t splits_override);
+torch::Tensor gemm_mxfp4(
+    torch::Tensor packed, torch::Tensor scales, torch::Tensor x, c10::optional<torch::Tensor> bias);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rms_norm", &rms_norm, "RMSNorm (bf16 -> bf16)");
@@ -132,4 +141,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dense prefill MFMA GEMM x[M,in] @ int8 W[in,out] (+bias) -> bf16, column scale in the "
         "epilogue",
         py::arg("q8"), py::arg("scale8"), py::arg("x"), py::arg("bias") = py::none());
+  m.def("mxfp4_quantize", &mxfp4_quantize,
+        "OCP MXFP4 quantize [in,out] bf16 -> (packed u8 [in/2,out], E8M0 scales u8 [in/32,out])");
+  m.def("mxfp4_dequantize", &mxfp4_dequantize, "MXFP4 -> bf16 [in,out]");
+  m.def("gemv_mxfp4", &gemv_mxfp4,
+        "split-K MXFP4 gemv (hardware fp4 dequant, E8M0 block scales) with epilogue",
+        py::arg("packed"), py::arg("scales"), py::arg("x"), py::arg("workspace"),
+        py::arg("residual"), py::arg("epilogue"), py::arg("splits") = 0, py::arg("bias") = py::none());
+  m.def("gemv_mxfp4_splits", &gemv_mxfp4_splits,
+        "split count gemv_mxfp4 uses for (in, out, batch) — sizes the workspace",
+        py::arg("in_dim"), py::arg("out_dim"), py::arg("batch"), py::arg("splits") = 0);
+  m.def("gemm_mxfp4", &gemm_mxfp4,
+        "dense prefill MFMA GEMM x[M,in] @ MXFP4 W[in,out] (+bias) -> bf16, hardware fp4 dequant "
+        "fused into the LDS staging",
+        py::arg("packed"), py::arg("scales"), py::arg("x"), py::arg("bias") = py::none());
 }

@@ -6,6 +6,8 @@
 //   nf4:  packed u8 [in, out/2] (even column = low nibble),
 //         absmax bf16 [in, out/64] (blocks of 64 along out)
 //   int8: q8 s8 [in, out], scale8 bf16 [out] (per output column)
+//   mxfp4: packed u8 [in/2, out] (rows 2j / 2j+1 = low / high nibble),
+//         scales u8 [in/32, out] (E8M0, blocks of 32 along in; ops/mxfp4.py)
 //
 // One 256-thread workgroup owns a 128x128 C tile: 4 waves as 2x2, each with
 // 4x4 mfma_f32_16x16x32_bf16 accumulator blocks (64 accumulator VGPRs). The
@@ -21,7 +23,11 @@
 // NF4 elements are bf16(LUT[nibble] * float(absmax)), bit for bit what
 // nf4_dequantize writes, so the fused path differs from dequant + matmul only
 // in summation order. int8 stages the s8 value as bf16 (exact) and applies
-// the column scale to the fp32 accumulator in the epilogue.
+// the column scale to the fp32 accumulator in the epilogue. MXFP4 needs no
+// LUT: a thread's two 8-byte packed loads hold its 4 k rows x 8 columns, and
+// per column two v_cvt_scalef32_pk_bf16_fp4 (byte = two consecutive k, one
+// shared power-of-two scale, exact) give the 4 bf16 of the ds_write_b64. The
+// elements are bit for bit what mxfp4_dequantize writes.
 //
 // Rows >= M and columns >= out are never loaded and never stored: their
 // fragments are zero-filled. Requires in % 64 == 0 and out % 64 == 0.
@@ -74,10 +80,29 @@ __device__ __forceinline__ unsigned int gq_s8_bf16(unsigned int word, int byte) 
   return __float_as_uint((float)v) >> 16;
 }
 
-template <bool NF4, bool SPLIT>
+enum GqMode : int { GQ_NF4 = 0, GQ_INT8 = 1, GQ_MXFP4 = 2 };
+
+// byte BYTE of `word` (two consecutive-k fp4 of one column) * scale -> packed
+// bf16 pair, low nibble in the low half
+template <int BYTE>
+__device__ __forceinline__ unsigned int gq_fp4_bf16x2(unsigned int word, float scale) {
+  const bf16x2_gq r = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, scale, BYTE);
+  return __builtin_bit_cast(unsigned int, r);
+}
+
+template <int BYTE>
+__device__ __forceinline__ uint2 gq_fp4_quad(unsigned int w01, unsigned int w23, unsigned int s4) {
+  const float sc = __uint_as_float(((s4 >> (8 * BYTE)) & 0xFFu) << 23);
+  uint2 o;
+  o.x = gq_fp4_bf16x2<BYTE>(w01, sc);
+  o.y = gq_fp4_bf16x2<BYTE>(w23, sc);
+  return o;
+}
+
+template <GqMode MODE, bool SPLIT>
 __global__ __launch_bounds__(256) void gemm_quant_kernel(
-    const unsigned char* __restrict__ wq,        // nf4: packed [in, out/2]; int8: q8 [in, out]
-    const unsigned short* __restrict__ wscale,   // nf4: absmax [in, out/64]; int8: scale8 [out]
+    const unsigned char* __restrict__ wq,        // nf4: packed [in, out/2]; int8: q8 [in, out]; mxfp4: packed [in/2, out]
+    const void* __restrict__ wscale_v,           // nf4: absmax [in, out/64]; int8: scale8 [out]; mxfp4: scales u8 [in/32, out]
     const unsigned short* __restrict__ x,        // [M, in] bf16
     const unsigned short* __restrict__ bias,     // [out] bf16 or null
     unsigned short* __restrict__ c,              // [M, out] bf16 (SPLIT: unused)
@@ -86,6 +111,9 @@ __global__ __launch_bounds__(256) void gemm_quant_kernel(
     int in_dim,
     int out_dim,
     int ksteps_per_split) {
+  constexpr bool NF4 = MODE == GQ_NF4;
+  constexpr bool MX = MODE == GQ_MXFP4;
+  const unsigned short* wscale = reinterpret_cast<const unsigned short*>(wscale_v);
   __shared__ __attribute__((aligned(16))) unsigned char lds[GQ_LDS_B];
   float2* lut2 = reinterpret_cast<float2*>(lds);
 
@@ -114,7 +142,7 @@ __global__ __launch_bounds__(256) void gemm_quant_kernel(
   const bool b_live = n0 + nloc < out_dim;  // out % 64 == 0: all 8 columns in or out
 
   uint4 ra[4];
-  unsigned int rb[4][2];  // nf4 uses word 0 only
+  unsigned int rb[4][2];  // nf4 uses word 0 only; mxfp4: rows [0], [1] = k pairs, [2][0..1] = scales
   float am[4];
 
   auto load_tiles = [&](int kt) {
@@ -124,6 +152,24 @@ __global__ __launch_bounds__(256) void gemm_quant_kernel(
       ra[i] = make_uint4(0u, 0u, 0u, 0u);
       if (m < M)
         ra[i] = *reinterpret_cast<const uint4*>(x + (size_t)m * in_dim + kt + a_chunk * 8);
+    }
+    if (MX) {
+      // 4 k rows = packed rows k/2, k/2+1; kt and kq*4 are multiples of 4, so
+      // the rows never straddle a 32-row scale block
+      const size_t k = (size_t)(kt + kq * 4);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) rb[j][0] = rb[j][1] = 0u;
+      if (b_live) {
+        const unsigned char* p = wq + (k >> 1) * (size_t)out_dim + n0 + nloc;
+        const uint2 q0 = *reinterpret_cast<const uint2*>(p);
+        const uint2 q1 = *reinterpret_cast<const uint2*>(p + out_dim);
+        const uint2 s8 = *reinterpret_cast<const uint2*>(
+            reinterpret_cast<const unsigned char*>(wscale_v) + (k >> 5) * (size_t)out_dim + n0 + nloc);
+        rb[0][0] = q0.x; rb[0][1] = q0.y;
+        rb[1][0] = q1.x; rb[1][1] = q1.y;
+        rb[2][0] = s8.x; rb[2][1] = s8.y;
+      }
+      return;
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -151,7 +197,17 @@ __global__ __launch_bounds__(256) void gemm_quant_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       *reinterpret_cast<uint4*>(&at[GQ_BYTE(a_row + 32 * i, a_chunk * 16)]) = ra[i];
-    if (NF4) {
+    if (MX) {
+      // a dead thread staged zero bytes and a zero scale byte: +0 * 2^-127
+      *reinterpret_cast<uint2*>(&bt[GQ_BYTE(nloc + 0, kq * 8)]) = gq_fp4_quad<0>(rb[0][0], rb[1][0], rb[2][0]);
+      *reinterpret_cast<uint2*>(&bt[GQ_BYTE(nloc + 1, kq * 8)]) = gq_fp4_quad<1>(rb[0][0], rb[1][0], rb[2][0]);
+      *reinterpret_cast<uint2*>(&bt[GQ_BYTE(nloc + 2, kq * 8)]) = gq_fp4_quad<2>(rb[0][0], rb[1][0], rb[2][0]);
+      *reinterpret_cast<uint2*>(&bt[GQ_BYTE(nloc + 3, kq * 8)]) = gq_fp4_quad<3>(rb[0][0], rb[1][0], rb[2][0]);
+      *reinterpret_cast<uint2*>(&bt[GQ_BYTE(nloc + 4, kq * 8)]) = gq_fp4_quad<0>(rb[0][1], rb[1][1], rb[2][1]);
+      *reinterpret_cast<uint2*>(&bt[GQ_BYTE(nloc + 5, kq * 8)]) = gq_fp4_quad<1>(rb[0][1], rb[1][1], rb[2][1]);
+      *reinterpret_cast<uint2*>(&bt[GQ_BYTE(nloc + 6, kq * 8)]) = gq_fp4_quad<2>(rb[0][1], rb[1][1], rb[2][1]);
+      *reinterpret_cast<uint2*>(&bt[GQ_BYTE(nloc + 7, kq * 8)]) = gq_fp4_quad<3>(rb[0][1], rb[1][1], rb[2][1]);
+    } else if (NF4) {
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
         float2 w2[4];
@@ -251,7 +307,7 @@ __global__ __launch_bounds__(256) void gemm_quant_kernel(
     if (n >= out_dim) continue;  // out % 64 == 0: the 4 columns are all in or all out
     float sc[4] = {1.f, 1.f, 1.f, 1.f};
     float bs[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!NF4) {
+    if (MODE == GQ_INT8) {
       const uint2 s = *reinterpret_cast<const uint2*>(wscale + n);
       sc[0] = bf16_to_f32((unsigned short)(s.x & 0xFFFFu));
       sc[1] = bf16_to_f32((unsigned short)(s.x >> 16));
@@ -273,7 +329,7 @@ __global__ __launch_bounds__(256) void gemm_quant_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         v[r] = acc[rbk][nb][r];
-        if (!NF4) v[r] *= sc[r];
+        if (MODE == GQ_INT8) v[r] *= sc[r];
         if (bias != nullptr) v[r] += bs[r];
       }
       uint2 o;
@@ -286,7 +342,7 @@ __global__ __launch_bounds__(256) void gemm_quant_kernel(
 
 // split-K phase 2: one thread per 4 consecutive columns of one row sums the
 // slices in index order, then the same epilogue as the direct kernel
-template <bool NF4>
+template <GqMode MODE>
 __global__ __launch_bounds__(256) void gemm_quant_reduce_kernel(
     const float* __restrict__ ws,               // [splits, M, out]
     const unsigned short* __restrict__ wscale,  // int8: scale8 [out]
@@ -304,7 +360,7 @@ __global__ __launch_bounds__(256) void gemm_quant_reduce_kernel(
     s += p;
   }
   float v[4] = {s[0], s[1], s[2], s[3]};
-  if (!NF4) {
+  if (MODE == GQ_INT8) {
     const uint2 q = *reinterpret_cast<const uint2*>(wscale + n);
     v[0] *= bf16_to_f32((unsigned short)(q.x & 0xFFFFu));
     v[1] *= bf16_to_f32((unsigned short)(q.x >> 16));
@@ -346,7 +402,7 @@ static void gq_check_common(const torch::Tensor& x, const c10::optional<torch::T
   }
 }
 
-template <bool NF4>
+template <GqMode MODE>
 static torch::Tensor gq_launch(const torch::Tensor& wq, const torch::Tensor& wscale, const torch::Tensor& x,
                                const c10::optional<torch::Tensor>& bias, int64_t in_dim, int64_t out_dim) {
   const int64_t M = x.size(0);
@@ -362,7 +418,7 @@ static torch::Tensor gq_launch(const torch::Tensor& wq, const torch::Tensor& wsc
     splits = (nk + per - 1) / per;
   }
   const unsigned char* wq_p = reinterpret_cast<const unsigned char*>(wq.data_ptr());
-  const unsigned short* ws_p = reinterpret_cast<const unsigned short*>(wscale.data_ptr());
+  const void* ws_p = wscale.data_ptr();
   const unsigned short* x_p = reinterpret_cast<const unsigned short*>(x.data_ptr());
   const unsigned short* b_p =
       bias.has_value() ? reinterpret_cast<const unsigned short*>(bias->data_ptr()) : nullptr;
@@ -370,7 +426,7 @@ static torch::Tensor gq_launch(const torch::Tensor& wq, const torch::Tensor& wsc
   auto stream = at::cuda::getCurrentCUDAStream();
   if (splits < 2) {
     dim3 grid((unsigned)row_tiles, (unsigned)col_tiles);
-    gemm_quant_kernel<NF4, false><<<grid, 256, 0, stream>>>(
+    gemm_quant_kernel<MODE, false><<<grid, 256, 0, stream>>>(
         wq_p, ws_p, x_p, b_p, c_p, nullptr, (int)M, (int)in_dim, (int)out_dim, nk);
     HIP_CHECK_LAST();
     return c;
@@ -378,13 +434,13 @@ static torch::Tensor gq_launch(const torch::Tensor& wq, const torch::Tensor& wsc
   // every (slice, valid row, valid column) is written by phase 1 before phase 2 reads it
   auto part = torch::empty({(int64_t)splits, M, out_dim}, x.options().dtype(torch::kFloat32));
   dim3 grid((unsigned)row_tiles, (unsigned)col_tiles, (unsigned)splits);
-  gemm_quant_kernel<NF4, true><<<grid, 256, 0, stream>>>(
+  gemm_quant_kernel<MODE, true><<<grid, 256, 0, stream>>>(
       wq_p, ws_p, x_p, nullptr, nullptr, part.data_ptr<float>(), (int)M, (int)in_dim, (int)out_dim, per);
   HIP_CHECK_LAST();
   const long n_elems = (long)M * out_dim;
   const long threads = n_elems / 4;
-  gemm_quant_reduce_kernel<NF4><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
-      part.data_ptr<float>(), ws_p, b_p, c_p, n_elems, (int)out_dim, splits);
+  gemm_quant_reduce_kernel<MODE><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
+      part.data_ptr<float>(), reinterpret_cast<const unsigned short*>(ws_p), b_p, c_p, n_elems, (int)out_dim, splits);
   HIP_CHECK_LAST();
   return c;
 }
@@ -403,7 +459,7 @@ torch::Tensor gemm_nf4(
   gq_check_common(x, bias, in_dim, out_dim, "gemm_nf4");
   TORCH_CHECK(x.size(0) < (1 << 30), "gemm_nf4: too many rows");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(packed.data_ptr()) % 4 == 0, "gemm_nf4: packed must be 4-byte aligned");
-  return gq_launch<true>(packed, absmax, x, bias, in_dim, out_dim);
+  return gq_launch<GQ_NF4>(packed, absmax, x, bias, in_dim, out_dim);
 }
 
 torch::Tensor gemm_int8(
@@ -422,5 +478,24 @@ torch::Tensor gemm_int8(
   TORCH_CHECK(reinterpret_cast<uintptr_t>(q8.data_ptr()) % 8 == 0 &&
                   reinterpret_cast<uintptr_t>(scale8.data_ptr()) % 8 == 0,
               "gemm_int8: q8 and scale8 must be 8-byte aligned");
-  return gq_launch<false>(q8, scale8, x, bias, in_dim, out_dim);
+  return gq_launch<GQ_INT8>(q8, scale8, x, bias, in_dim, out_dim);
+}
+
+torch::Tensor gemm_mxfp4(
+    torch::Tensor packed,  // [in/2, out] u8
+    torch::Tensor scales,  // [in/32, out] u8 (E8M0)
+    torch::Tensor x,       // [M, in] bf16
+    c10::optional<torch::Tensor> bias) {
+  TORCH_CHECK(packed.is_cuda() && packed.dtype() == torch::kUInt8 && packed.dim() == 2 && packed.is_contiguous(),
+              "gemm_mxfp4: packed must be a contiguous u8 [in/2, out] GPU tensor");
+  const int64_t in_dim = packed.size(0) * 2, out_dim = packed.size(1);
+  TORCH_CHECK(scales.is_cuda() && scales.dtype() == torch::kUInt8 && scales.dim() == 2 &&
+                  scales.is_contiguous() && scales.size(0) * 32 == in_dim && scales.size(1) == out_dim,
+              "gemm_mxfp4: scales must be a contiguous u8 [in/32, out] GPU tensor");
+  gq_check_common(x, bias, in_dim, out_dim, "gemm_mxfp4");
+  TORCH_CHECK(x.size(0) < (1 << 30), "gemm_mxfp4: too many rows");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(packed.data_ptr()) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(scales.data_ptr()) % 8 == 0,
+              "gemm_mxfp4: packed and scales must be 8-byte aligned");
+  return gq_launch<GQ_MXFP4>(packed, scales, x, bias, in_dim, out_dim);
 }

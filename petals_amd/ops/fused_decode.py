@@ -112,8 +112,10 @@ def set_prefill_gemm_mode(mode: str) -> None:
 # the measured crossover against dequantize + rocBLAS over the llama-2-70b
 # projection shapes (profiles/prefill_gemm_fused.log: NF4 wins everywhere at
 # 256 rows and loses at 512; int8, whose dequant is three torch passes, still
-# wins at 512 and loses at 2048). Larger chunks stay on dense() in any mode.
-FUSED_GEMM_MAX_ROWS = {"nf4": 256, "int8": 512}
+# wins at 512 and loses at 2048; MXFP4 wins everywhere at 256 and loses on qkv
+# and gate+up at 512, profiles/mxfp4.log). Larger chunks stay on dense() in any
+# mode.
+FUSED_GEMM_MAX_ROWS = {"nf4": 256, "int8": 512, "mxfp4": 256}
 
 
 def fused_gemm_eligible(quant: str, rows: int, in_dim: int, out_dim: int) -> bool:
@@ -130,9 +132,10 @@ def fused_gemm_eligible(quant: str, rows: int, in_dim: int, out_dim: int) -> boo
 
 
 class _FastWeight:
-    """A transposed [in, out] weight in bf16, NF4 or weight-only int8
+    """A transposed [in, out] weight in bf16, NF4, MXFP4 or weight-only int8
     (quantize-on-load; int8 = per-out-column symmetric absmax, the MI355X
-    stand-in for the reference's optional LLM.int8 path).
+    stand-in for the reference's optional LLM.int8 path; mxfp4 = OCP E2M1
+    elements with an E8M0 scale per 32 input rows, ops/mxfp4.py).
 
     Split-K counts are autotuned once per (kind, in, out) shape at load time
     (profiles/gemv_split_sweep.log shows the optimum varies ~2x by shape);
@@ -143,7 +146,16 @@ class _FastWeight:
         self.quant = quant
         self.in_dim, self.out_dim = t_bf16.shape
         self.t = self.packed = self.absmax = self.absmax_t = self.q8 = self.scale8 = None
-        if quant == "nf4":
+        self.mx_packed = self.mx_scales = None
+        if quant == "mxfp4":
+            from petals_amd.ops import mxfp4
+
+            mxfp4.check_shape(self.in_dim, self.out_dim)
+            if t_bf16.is_cuda:
+                self.mx_packed, self.mx_scales = hip.mxfp4_quantize(t_bf16.to(torch.bfloat16).contiguous())
+            else:  # CPU blocks (tests, tooling): the torch reference, bit-identical
+                self.mx_packed, self.mx_scales = mxfp4.quantize(t_bf16.to(torch.bfloat16))
+        elif quant == "nf4":
             self.packed, self.absmax = hip.nf4_quantize(t_bf16.contiguous())
             # transposed absmax copy: one contiguous 32 B load per 16-row
             # unroll block in the gemv instead of 16 strided 2 B gathers
@@ -171,6 +183,11 @@ class _FastWeight:
         elif self.quant == "int8":
             candidates = [0, 16, 32, 64, 128, 192]
             max_chunk = 128
+        elif self.quant == "mxfp4":
+            # chunks are whole 32-row blocks; at most 64 splits so splits * out
+            # partials fit the fast paths' 64 * B * max_out workspace
+            candidates = [0, 8, 16, 24, 32, 48, 64]
+            max_chunk = 32
         else:
             candidates = [0, 8, 16, 32, 64, 128]
             max_chunk = 64
@@ -206,6 +223,8 @@ class _FastWeight:
         assert x_parts is None and sumsq_out is None, "folded-norm gemv is NF4-only"
         if self.quant == "int8":
             return self.hip.gemv_int8(self.q8, self.scale8, x, ws, residual, epilogue, splits, bias)
+        if self.quant == "mxfp4":
+            return self.hip.gemv_mxfp4(self.mx_packed, self.mx_scales, x, ws, residual, epilogue, splits, bias)
         return self.hip.gemv_bf16(self.t, x, ws, residual, epilogue, splits, bias)
 
     def gemv(self, x, ws, residual, epilogue, bias=None, x_parts=None, fold_eps=0.0, sumsq_out=None):
@@ -224,6 +243,12 @@ class _FastWeight:
             return _dequant_cached(
                 self, lambda: (self.q8.to(torch.float32) * self.scale8.float()).to(torch.bfloat16)
             )
+        if self.quant == "mxfp4":
+            if not self.mx_packed.is_cuda:
+                from petals_amd.ops import mxfp4
+
+                return mxfp4.dequantize(self.mx_packed, self.mx_scales)
+            return _dequant_cached(self, lambda: self.hip.mxfp4_dequantize(self.mx_packed, self.mx_scales))
         return self.t
 
     def matmul(self, x: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -241,6 +266,8 @@ class _FastWeight:
             x2 = x.reshape(-1, self.in_dim).contiguous()
             if self.quant == "nf4":
                 out = self.hip.gemm_nf4(self.packed, self.absmax, x2, bias)
+            elif self.quant == "mxfp4":
+                out = self.hip.gemm_mxfp4(self.mx_packed, self.mx_scales, x2, bias)
             else:
                 out = self.hip.gemm_int8(self.q8, self.scale8, x2, bias)
             return out.view(*x.shape[:-1], self.out_dim)
