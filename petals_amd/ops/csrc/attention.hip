@@ -8,10 +8,10 @@
 // (same as the prefill kernel); 4 waves take interleaved 32-key tiles of the
 // workgroup's split range and combine through LDS; attn_decode_combine merges
 // splits. Measured (scripts/decode_mfma.hip, llama-2-70b shape): 1039 GB/s at
-// kv=4k -> 3509 GB/s at kv=131k, 2.2-2.4x the VALU kernel at every length.
+// kv=4k -> 3509 GB/s at kv=131k, 2.2-2.4x the original VALU kernel (16-lane-
+// group dot products, online softmax in registers; removed, see
+// docs/KERNELS.md) at every length.
 //
-// The original VALU kernel (attn_decode_kernel: 16-lane-group dot products,
-// online softmax in registers) is kept behind PETALS_DECODE_KERNEL=valu.
 // kv_len comes from a DEVICE pointer so the whole decode step can be captured
 // in a hipGraph with a moving position.
 //
@@ -21,8 +21,6 @@
 #include "common.h"
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
-
-#include <cstdlib>
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -256,144 +254,6 @@ __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
   }
 }
 
-template <int HD, int GQ>
-__global__ __launch_bounds__(64) void attn_decode_kernel(
-    const float* __restrict__ q,           // [B, KV, GQ, HD]
-    const unsigned short* __restrict__ k_cache,  // [Bc, KV, Lmax, HD]
-    const unsigned short* __restrict__ v_cache,
-    float* __restrict__ part_o,            // [B*KV, splits, GQ, HD]
-    float* __restrict__ part_ml,           // [B*KV, splits, GQ, 2]
-    const int* __restrict__ kv_len_ptr,
-    const float* __restrict__ alibi,  // [kv_heads*GQ] slopes or null (ALiBi adds slope*j; the
-                                      // row-constant part of the bias cancels in softmax)
-    int kv_heads,
-    int lmax,
-    int n_splits,
-    float scale) {
-  constexpr int LANES_PER_ROW = 16;
-  constexpr int EPL = HD / LANES_PER_ROW;  // elems per lane (8 for HD=128)
-  constexpr int GROUPS = WAVE / LANES_PER_ROW;  // 4 rows in flight
-
-  const int bkv = blockIdx.x;
-  const int b = bkv / kv_heads;
-  const int kv = bkv - b * kv_heads;
-  const int split = blockIdx.y;
-  const int kv_len = *kv_len_ptr;
-
-  const int rows_per_split = (kv_len + n_splits - 1) / n_splits;
-  const int j_begin = split * rows_per_split;
-  const int j_end = min(j_begin + rows_per_split, kv_len);
-
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int grp = lane / LANES_PER_ROW;  // 0..3
-  const int gl = lane & (LANES_PER_ROW - 1);  // lane within group
-
-  // stage q in LDS (scaled)
-  __shared__ float q_lds[GQ][HD];
-  for (int idx = threadIdx.x; idx < GQ * HD; idx += WAVE) {
-    q_lds[idx / HD][idx % HD] = q[((size_t)(b * kv_heads + kv) * GQ) * HD + idx] * scale;
-  }
-  __syncthreads();
-
-  float m[GQ], l[GQ], o[GQ][EPL];
-#pragma unroll
-  for (int g = 0; g < GQ; ++g) {
-    m[g] = NEG_SENTINEL;
-    l[g] = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) o[g][e] = 0.f;
-  }
-
-  const unsigned short* k_base = k_cache + ((size_t)b * kv_heads + kv) * lmax * HD;
-  const unsigned short* v_base = v_cache + ((size_t)b * kv_heads + kv) * lmax * HD;
-
-  float sl[GQ];
-#pragma unroll
-  for (int g = 0; g < GQ; ++g) sl[g] = alibi ? alibi[kv * GQ + g] : 0.f;
-
-  for (int j = j_begin + grp; j < j_end; j += GROUPS) {
-    // load K row slice: 16 lanes x EPL elems, coalesced
-    const unsigned short* krow = k_base + (size_t)j * HD + gl * EPL;
-    float kf[EPL];
-    if (EPL == 8) {
-      const short8 k8 = *reinterpret_cast<const short8*>(krow);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) kf[e] = bf16_to_f32((unsigned short)k8[e]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) kf[e] = bf16_to_f32(krow[e]);
-    }
-    // scores for each q head of this group
-    float s[GQ];
-#pragma unroll
-    for (int g = 0; g < GQ; ++g) {
-      float partial = 0.f;
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) partial = fmaf(kf[e], q_lds[g][gl * EPL + e], partial);
-      s[g] = group16_reduce_sum(partial) + sl[g] * j;  // all lanes get the row score
-    }
-    // V row slice
-    const unsigned short* vrow = v_base + (size_t)j * HD + gl * EPL;
-    float vf[EPL];
-    if (EPL == 8) {
-      const short8 v8 = *reinterpret_cast<const short8*>(vrow);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) vf[e] = bf16_to_f32((unsigned short)v8[e]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) vf[e] = bf16_to_f32(vrow[e]);
-    }
-#pragma unroll
-    for (int g = 0; g < GQ; ++g) {
-      const float m_new = fmaxf(m[g], s[g]);
-      const float corr = __expf(m[g] - m_new);
-      const float p = __expf(s[g] - m_new);
-      l[g] = l[g] * corr + p;
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) o[g][e] = o[g][e] * corr + p * vf[e];
-      m[g] = m_new;
-    }
-  }
-
-  // combine the 4 row-groups through LDS (deterministic order)
-  __shared__ float c_m[GROUPS][GQ];
-  __shared__ float c_l[GROUPS][GQ];
-  __shared__ float c_o[GROUPS][GQ][HD];
-  if (gl * EPL < HD) {
-#pragma unroll
-    for (int g = 0; g < GQ; ++g) {
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) c_o[grp][g][gl * EPL + e] = o[g][e];
-      if (gl == 0) {
-        c_m[grp][g] = m[g];
-        c_l[grp][g] = l[g];
-      }
-    }
-  }
-  __syncthreads();
-
-  float* po = part_o + (((size_t)bkv * n_splits + split) * GQ) * HD;
-  float* pml = part_ml + (((size_t)bkv * n_splits + split) * GQ) * 2;
-  for (int idx = threadIdx.x; idx < GQ * HD; idx += WAVE) {
-    const int g = idx / HD, d = idx % HD;
-    float m_star = c_m[0][g];
-#pragma unroll
-    for (int r = 1; r < GROUPS; ++r) m_star = fmaxf(m_star, c_m[r][g]);
-    float osum = 0.f, lsum = 0.f;
-#pragma unroll
-    for (int r = 0; r < GROUPS; ++r) {
-      const float w = (c_m[r][g] <= NEG_THRESHOLD) ? 0.f : __expf(c_m[r][g] - m_star);
-      osum += w * c_o[r][g][d];
-      lsum += w * c_l[r][g];
-    }
-    po[idx] = osum;
-    if (d == 0) {
-      pml[g * 2 + 0] = m_star;
-      pml[g * 2 + 1] = lsum;
-    }
-  }
-}
-
 __global__ void attn_decode_combine_kernel(
     const float* __restrict__ part_o,   // [B*KV, splits, GQ, HD]
     const float* __restrict__ part_ml,  // [B*KV, splits, GQ, 2]
@@ -438,40 +298,24 @@ torch::Tensor attn_decode_fused(
   const int b = q.size(0);
   const int kv_heads = k_cache.size(1), lmax = k_cache.size(2), hd = k_cache.size(3);
   const int GQi = (int)gq;
-  static const bool use_valu = [] {
-    const char* s = std::getenv("PETALS_DECODE_KERNEL");
-    return s && s[0] == 'v';
-  }();
   int n_splits = (int)n_splits_i;
   if (n_splits <= 0) {
+    // 4-wave workgroups; fill ~256 CUs (chunks >= 128 rows) and go up to
+    // 3 wgs/CU only when chunks stay >= 512 rows (measured knees,
+    // profiles/decode_longctx_sweep.log + scripts/decode_mfma.hip).
+    // Forcing one split at short caches to skip the combine kernel LOST
+    // 1.4 tok/s end to end (profiles/attn_direct_ab.log): halving the split
+    // occupancy costs more than the removed launch.
     const int bkv = std::max(1, b * kv_heads);
-    if (use_valu) {
-      // VALU kernel: target ~1024 single-wave workgroups, chunks >= 64 rows
-      n_splits = std::max(1, std::min(1024 / bkv, (lmax + 63) / 64));
-    } else {
-      // MFMA kernel: 4-wave workgroups; fill ~256 CUs (chunks >= 128 rows) and
-      // go up to 3 wgs/CU only when chunks stay >= 512 rows (measured knees,
-      // profiles/decode_longctx_sweep.log + scripts/decode_mfma.hip)
-      const int by_occ = std::min(768 / bkv, lmax / 512);
-      const int by_min = std::min(256 / bkv, (lmax + 127) / 128);
-      n_splits = std::max(1, std::max(by_occ, by_min));
-      // measured dead end (profiles/attn_direct_ab.log): forcing one split
-      // + in-kernel normalization (combine kernel skipped) at short caches
-      // LOST 1.4 tok/s end to end — halving the split occupancy costs more
-      // than the removed launch. Off by default; the env knob keeps the
-      // single-split direct-out path selectable for re-evaluation.
-      static const int short_max = [] {
-        const char* e = std::getenv("PETALS_AMD_DECODE_SHORT_LMAX");
-        return e ? std::atoi(e) : 0;
-      }();
-      if (lmax <= short_max) n_splits = 1;
-    }
+    const int by_occ = std::min(768 / bkv, lmax / 512);
+    const int by_min = std::min(256 / bkv, (lmax + 127) / 128);
+    n_splits = std::max(1, std::max(by_occ, by_min));
   }
   auto opts = q.options();
-  const bool will_direct = !use_valu && n_splits == 1;  // parts go unused
-  if (!will_direct && part_o.numel() < (int64_t)b * kv_heads * n_splits * GQi * hd)
+  const bool direct = n_splits == 1;  // parts go unused
+  if (!direct && part_o.numel() < (int64_t)b * kv_heads * n_splits * GQi * hd)
     part_o = torch::empty({(int64_t)b * kv_heads, n_splits, GQi, hd}, opts);
-  if (!will_direct && part_ml.numel() < (int64_t)b * kv_heads * n_splits * GQi * 2)
+  if (!direct && part_ml.numel() < (int64_t)b * kv_heads * n_splits * GQi * 2)
     part_ml = torch::empty({(int64_t)b * kv_heads, n_splits, GQi, 2}, opts);
   auto out = torch::empty({(int64_t)b, (int64_t)kv_heads * GQi * hd}, opts);
 
@@ -491,39 +335,24 @@ torch::Tensor attn_decode_fused(
     alibi_p = alibi_slopes->data_ptr<float>();
   }
 
-  // single split on the MFMA path: the decode kernel normalizes and writes
-  // the output itself — the combine kernel (pure launch latency at short kv)
-  // is skipped entirely
-  float* direct_p = (!use_valu && n_splits == 1) ? out.data_ptr<float>() : nullptr;
+  // single split: the decode kernel normalizes and writes the output itself —
+  // the combine kernel (pure launch latency at short kv) is skipped entirely
+  float* direct_p = direct ? out.data_ptr<float>() : nullptr;
   bool launched = false;
 #define ATTN_CASE(HDV, GQV)                                                   \
   if (hd == HDV && GQi == GQV) {                                              \
-    if (use_valu)                                                             \
-      attn_decode_kernel<HDV, GQV><<<grid, 64, 0, stream>>>(                  \
-          qp, kp, vp, pop, pmlp, lenp, alibi_p, kv_heads, lmax, n_splits, sc);\
-    else                                                                      \
-      mfma_decode_kernel<HDV, GQV><<<grid, DWAVES * WAVE, 0, stream>>>(       \
-          qp, kp, vp, pop, pmlp, lenp, alibi_p, kv_heads, lmax, n_splits, sc, \
-          direct_p);                                                          \
-    launched = true;                                                          \
-  }
-  ATTN_CASE(128, 1) ATTN_CASE(128, 2) ATTN_CASE(128, 4) ATTN_CASE(128, 6)
-  ATTN_CASE(128, 8) ATTN_CASE(128, 16)
-  ATTN_CASE(64, 1) ATTN_CASE(64, 2) ATTN_CASE(64, 4) ATTN_CASE(64, 8) ATTN_CASE(64, 16)
-#undef ATTN_CASE
-  // GQ > 16 (multi-group MFMA path only; the VALU kernel would blow its
-  // per-lane register arrays): falcon-7b MQA (gq=71), falcon-180b (gq=29)
-#define ATTN_CASE_BIG(HDV, GQV)                                               \
-  if (hd == HDV && GQi == GQV) {                                              \
-    TORCH_CHECK(!use_valu, "VALU decode kernel does not support gq=", GQV);   \
     mfma_decode_kernel<HDV, GQV><<<grid, DWAVES * WAVE, 0, stream>>>(         \
         qp, kp, vp, pop, pmlp, lenp, alibi_p, kv_heads, lmax, n_splits, sc,   \
         direct_p);                                                            \
     launched = true;                                                          \
   }
-  ATTN_CASE_BIG(64, 29) ATTN_CASE_BIG(64, 71) ATTN_CASE_BIG(64, 32)
-  ATTN_CASE_BIG(128, 32)
-#undef ATTN_CASE_BIG
+  ATTN_CASE(128, 1) ATTN_CASE(128, 2) ATTN_CASE(128, 4) ATTN_CASE(128, 6)
+  ATTN_CASE(128, 8) ATTN_CASE(128, 16)
+  ATTN_CASE(64, 1) ATTN_CASE(64, 2) ATTN_CASE(64, 4) ATTN_CASE(64, 8) ATTN_CASE(64, 16)
+  // GQ > 16 (multi-group): falcon-7b MQA (gq=71), falcon-180b (gq=29)
+  ATTN_CASE(64, 29) ATTN_CASE(64, 71) ATTN_CASE(64, 32)
+  ATTN_CASE(128, 32)
+#undef ATTN_CASE
   TORCH_CHECK(launched, "unsupported (head_dim, gqa) = (", hd, ", ", GQi, ")");
   HIP_CHECK_LAST();
 

@@ -36,13 +36,6 @@ __device__ __forceinline__ float wave_reduce_max(float x) {
   return x;
 }
 
-// sum across a 16-lane subgroup (lanes with equal lane/16)
-__device__ __forceinline__ float group16_reduce_sum(float x) {
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) x += __shfl_xor(x, off, WAVE);
-  return x;
-}
-
 #define HIP_CHECK_LAST()                                                     \
   do {                                                                       \
     hipError_t e = hipGetLastError();                                        \

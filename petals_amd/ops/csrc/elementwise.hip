@@ -429,11 +429,10 @@ __global__ void rope_cache_write_kernel(
 // families) — one fewer kernel per block on the decode path.
 #define QKV_RED_GROUPS 16  // 16 split groups x 64 outputs (1024-thread wgs):
 // halves each thread's serial split chain vs 8 — measured +0.9-1.0 tok/s on
-// every alternating pair (profiles/qrr_groups_ab.log); PETALS_QRR_GROUPS=8
-// selects the old width
+// every alternating pair (profiles/qrr_groups_ab.log)
 
-template <bool ROPE, int G_T = QKV_RED_GROUPS>
-__global__ __launch_bounds__(64 * G_T) void qkv_rope_reduce_kernel(
+template <bool ROPE>
+__global__ __launch_bounds__(64 * QKV_RED_GROUPS) void qkv_rope_reduce_kernel(
     const float* __restrict__ partials,  // [splits, b, row_elems]
     const float* __restrict__ cos_t,     // [max_pos, hd]
     const float* __restrict__ sin_t,
@@ -443,7 +442,7 @@ __global__ __launch_bounds__(64 * G_T) void qkv_rope_reduce_kernel(
     unsigned short* __restrict__ k_cache,  // [bcap, kh, lmax, hd]
     unsigned short* __restrict__ v_cache,
     int n_splits, int b, int qh, int kh, int lmax, int hd) {
-  constexpr int G = G_T;
+  constexpr int G = QKV_RED_GROUPS;
   __shared__ float acc_a[G][64];
   __shared__ float acc_b[G][64];
   const int half = hd >> 1;
@@ -540,23 +539,15 @@ torch::Tensor qkv_rope_reduce(
     TORCH_CHECK(bias->numel() == partials.size(2));
     bp = reinterpret_cast<const unsigned short*>(bias->data_ptr());
   }
-  static const int qrr_g = [] {
-    const char* e = std::getenv("PETALS_QRR_GROUPS");
-    return e ? std::atoi(e) : QKV_RED_GROUPS;
-  }();
-#define LAUNCH_QRR_G(R, G)                                                     \
-  qkv_rope_reduce_kernel<R, G><<<blocks, 64 * G, 0, stream>>>(                 \
+#define LAUNCH_QRR(R)                                                          \
+  qkv_rope_reduce_kernel<R><<<blocks, 64 * QKV_RED_GROUPS, 0, stream>>>(       \
       partials.data_ptr<float>(), cp, sp, pos.data_ptr<int>(), bp,             \
       q_out.data_ptr<float>(),                                                 \
       reinterpret_cast<unsigned short*>(k_cache.data_ptr()),                   \
       reinterpret_cast<unsigned short*>(v_cache.data_ptr()),                   \
       n_splits, b, (int)qh, (int)kh, lmax, hd)
-  if (qrr_g == 8) {
-    if (rope) LAUNCH_QRR_G(true, 8); else LAUNCH_QRR_G(false, 8);
-  } else {
-    if (rope) LAUNCH_QRR_G(true, 16); else LAUNCH_QRR_G(false, 16);
-  }
-#undef LAUNCH_QRR_G
+  if (rope) LAUNCH_QRR(true); else LAUNCH_QRR(false);
+#undef LAUNCH_QRR
   HIP_CHECK_LAST();
   return q_out;
 }
@@ -620,49 +611,4 @@ void rope_cache_write(
       reinterpret_cast<unsigned short*>(v_cache.data_ptr()),
       b, (int)qh, (int)kh, lmax, hd);
   HIP_CHECK_LAST();
-}
-
-// ---------------- row sum-of-squares (folded-RMSNorm first-block feeder) ----
-// One workgroup per row: parts layout matches gemv_reduce's sumsq_out
-// ([rows, 1] here — the consuming gemv sums n_parts entries either way).
-
-__global__ void sumsq_rows_kernel(
-    const unsigned short* __restrict__ x,  // [rows, dim] bf16
-    float* __restrict__ parts,             // [rows, 1]
-    int dim) {
-  const int row = blockIdx.x;
-  const unsigned short* xr = x + (size_t)row * dim;
-  float s = 0.f;
-  for (int i = threadIdx.x * 8; i + 8 <= dim; i += blockDim.x * 8) {
-    const short8 v = *reinterpret_cast<const short8*>(xr + i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float f = bf16_to_f32((unsigned short)v[j]);
-      s = fmaf(f, f, s);
-    }
-  }
-  for (int i = (dim & ~7) + threadIdx.x; i < dim; i += blockDim.x) {
-    const float f = bf16_to_f32(xr[i]);
-    s = fmaf(f, f, s);
-  }
-  __shared__ float red[1024 / WAVE];
-  s = wave_reduce_sum(s);
-  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < (int)(blockDim.x / WAVE); ++k) t += red[k];
-    parts[row] = t;
-  }
-}
-
-torch::Tensor sumsq_rows(torch::Tensor x) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.dim() == 2 && x.is_contiguous());
-  const int rows = x.size(0), dim = x.size(1);
-  auto parts = torch::empty({rows, 1}, x.options().dtype(torch::kFloat32));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  sumsq_rows_kernel<<<rows, 1024, 0, stream>>>(
-      reinterpret_cast<const unsigned short*>(x.data_ptr()), parts.data_ptr<float>(), dim);
-  HIP_CHECK_LAST();
-  return parts;
 }

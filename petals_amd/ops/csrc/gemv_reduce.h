@@ -8,7 +8,6 @@
 // ROCm-native stream API: this header is consumed verbatim (torch's hipify
 // only rewrites the .hip TUs, not local headers)
 #include <c10/hip/HIPStream.h>
-#include <cstdlib>
 
 enum GemvEpilogue : int {
   EPI_PLAIN_F32 = 0,     // y_f32[b, out] = sum
@@ -42,31 +41,25 @@ static __device__ __forceinline__ float gelu_tanh_f32(float x) {
   return 0.5f * x * (1.f + t);
 }
 
-// 512 threads = 64 outputs x 8 split groups per workgroup: the one-thread-
+// 1024 threads = 64 outputs x 16 split groups per workgroup: the one-thread-
 // per-output version launched only `out/64` single-wave workgroups (0.15
 // waves/SIMD for a 10k-output gemv) and was latency-bound at ~7 us — as much
-// as the small gemvs themselves. Split groups multiply resident waves 8x and
-// cut each thread's serial chain 8x; a tiny LDS tree combines (deterministic
-// order preserved: fixed group partition, fixed add order).
-#define GEMV_REDUCE_GROUPS 16  // 16 split groups x 64 outputs (1024-thread
-// wgs): halves each thread's serial split chain vs the round-2 value of 8 —
-// +1.3 tok/s on every alternating A/B pair (profiles/qrr_groups_ab.log);
-// PETALS_REDUCE_GROUPS=8 selects the old width
+// as the small gemvs themselves. Split groups multiply resident waves 16x and
+// cut each thread's serial chain 16x; a tiny LDS tree combines (deterministic
+// order preserved: fixed group partition, fixed add order). 16 groups beat 8
+// by +1.3 tok/s on every alternating A/B pair (profiles/qrr_groups_ab.log).
+#define GEMV_REDUCE_GROUPS 16
 
-template <int G>
-static __global__ __launch_bounds__(64 * G) void gemv_reduce_kernel_impl(
+static __global__ __launch_bounds__(64 * GEMV_REDUCE_GROUPS) void gemv_reduce_kernel(
     const float* __restrict__ partials,  // [n_splits, batch, out]
     const unsigned short* __restrict__ residual,  // [batch, out] or null
     const unsigned short* __restrict__ bias,      // [out] bf16 or null
     void* __restrict__ y,
-    float* __restrict__ sumsq_out,  // [batch, out/64] per-wg sum(y^2) or null —
-    // feeds the folded-RMSNorm decode path (the next gemv derives inv_rms from
-    // these instead of a separate norm kernel); computed over the bf16-ROUNDED
-    // stored values so it matches what a norm kernel reading y would see
     int n_splits,
     int batch,
     int out_dim,
     int epilogue) {
+  constexpr int G = GEMV_REDUCE_GROUPS;
   __shared__ float acc_g[G][64];
   __shared__ float acc_u[G][64];
   const int half = out_dim >> 1;
@@ -114,13 +107,7 @@ static __global__ __launch_bounds__(64 * G) void gemv_reduce_kernel_impl(
       reinterpret_cast<float*>(y)[row + o] = gelu_tanh_f32(sum);
     } else {  // EPI_RESIDUAL_BF16
       const float r = bf16_to_f32(residual[row + o]);
-      const unsigned short packed = f32_to_bf16(r + sum);
-      reinterpret_cast<unsigned short*>(y)[row + o] = packed;
-      if (sumsq_out) {
-        const float v = bf16_to_f32(packed);
-        float sq = wave_reduce_sum(v * v);  // 64 lanes of sg==0 = one wave
-        if (ol == 0) sumsq_out[(size_t)b * (out_dim >> 6) + (o >> 6)] = sq;
-      }
+      reinterpret_cast<unsigned short*>(y)[row + o] = f32_to_bf16(r + sum);
     }
   }
 }
@@ -135,8 +122,7 @@ static inline torch::Tensor launch_gemv_reduce(
     int out_dim,
     int epilogue,
     const torch::TensorOptions& f32_opts,
-    const torch::TensorOptions& bf16_opts,
-    c10::optional<torch::Tensor> sumsq_out = c10::nullopt) {
+    const torch::TensorOptions& bf16_opts) {
   const int half = out_dim / 2;
   const int n_out = (epilogue == EPI_SWIGLU_F32) ? half : out_dim;
   torch::Tensor y;
@@ -158,27 +144,11 @@ static inline torch::Tensor launch_gemv_reduce(
     TORCH_CHECK(bias->numel() == out_dim, "bias must be [out_dim] (pre-activation)");
     bias_p = reinterpret_cast<const unsigned short*>(bias->data_ptr());
   }
-  float* ss_p = nullptr;
-  if (sumsq_out.has_value() && sumsq_out->defined() && sumsq_out->numel() > 0) {
-    TORCH_CHECK(epilogue == EPI_RESIDUAL_BF16, "sumsq_out only with the residual epilogue");
-    TORCH_CHECK(out_dim % 64 == 0, "sumsq_out needs out_dim % 64 == 0");
-    TORCH_CHECK(sumsq_out->dtype() == torch::kFloat32 && sumsq_out->is_contiguous());
-    TORCH_CHECK(sumsq_out->numel() >= (int64_t)batch * (out_dim / 64));
-    ss_p = sumsq_out->data_ptr<float>();
-  }
   const int total = batch * n_out;
-  static const int red_g = [] {
-    const char* e = std::getenv("PETALS_REDUCE_GROUPS");
-    return e ? std::atoi(e) : GEMV_REDUCE_GROUPS;
-  }();
   int rblocks = (total + 63) / 64;
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  if (red_g == 16)
-    gemv_reduce_kernel_impl<16><<<rblocks, 64 * 16, 0, stream>>>(
-        partials.data_ptr<float>(), res_p, bias_p, y.data_ptr(), ss_p, n_splits, batch, out_dim, epilogue);
-  else
-    gemv_reduce_kernel_impl<8><<<rblocks, 64 * 8, 0, stream>>>(
-        partials.data_ptr<float>(), res_p, bias_p, y.data_ptr(), ss_p, n_splits, batch, out_dim, epilogue);
+  gemv_reduce_kernel<<<rblocks, 64 * GEMV_REDUCE_GROUPS, 0, stream>>>(
+      partials.data_ptr<float>(), res_p, bias_p, y.data_ptr(), n_splits, batch, out_dim, epilogue);
   HIP_CHECK_LAST();
   return y;
 }

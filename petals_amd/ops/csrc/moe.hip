@@ -22,6 +22,8 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <cstdlib>
+
 #ifndef GEMV_OUT_PER_WAVE
 #define GEMV_OUT_PER_WAVE 512
 #endif

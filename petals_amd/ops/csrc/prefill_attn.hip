@@ -8,9 +8,8 @@
 // softmax (per-lane row stats: the C-layout keeps each q row's 4 accumulator
 // rows in the same lane) -> P through a per-wave LDS round-trip into
 // A-fragment layout -> KVT/32*HD/16 PV MFMAs. Fragment layouts HW-verified by
-// scripts/mfma_verify.hip. KVT=64 default (amortizes softmax shuffles and
-// barriers over 2x the MFMA work vs KVT=32); PETALS_PREFILL_KVT=32 selects
-// the narrow tile for A/B.
+// scripts/mfma_verify.hip. KVT=64 amortizes softmax shuffles and barriers
+// over 2x the MFMA work vs the KVT=32 tile it replaced.
 //
 // Replaces the chunked rocBLAS-matmul + fp32-softmax prefill composition
 // (ops/reference.py attention) on the GPU path; the reference framework used
@@ -20,27 +19,27 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
-#include <cstdlib>
-
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 #define QTILE 16  // q rows per wave
 #define WAVES 4   // waves per workgroup
+#define KVT 64    // keys per K/V tile
 #define KPAD 8    // LDS row padding (elements) against bank conflicts
 
 // V-transpose LDS addressing: XOR swizzle on the dim-group (rows 8 apart land
 // 0 mod 128 B with any 16 B-aligned pitch, so the scalar transpose writes were
 // 16-way bank-conflicted — the dominant cost in the v1 PMC profile). Verified
 // injective with stage-write multiplicity 2 (b16 ideal) and PV-read
-// multiplicity 8 (b128 ideal) for both KVT=32 and KVT=64.
+// multiplicity 8 (b128 ideal).
 #define VT_BYTE(dim, key_byte) \
   ((((unsigned)(dim)) * ((KVT + KPAD) * 2) + (unsigned)(key_byte)) ^ ((((unsigned)(dim) >> 3) & 7u) << 4))
 
-// QR = q rows per wave (16 or 32). QR=32 runs NSET=2 16-row MFMA row sets per
-// wave off ONE K/V staging pass: staging traffic and barriers per flop halve,
-// at the cost of ~2x accumulator VGPRs and a larger per-wave P scratch.
-template <int HD, int KVT, bool ALIBI, int QR>
+// The loops over `qs` are written for NSET 16-row MFMA row sets per wave off
+// one K/V staging pass. NSET=2 (32 q rows per wave) lost its A/B
+// (profiles/prefill_qrows_ab.log) and is gone; the loop structure stays as it
+// was compiled, see the miscompile NOTE below before restructuring it.
+template <int HD, bool ALIBI>
 __global__ __launch_bounds__(WAVES * 64) void attn_prefill_kernel(
     const unsigned short* __restrict__ q,   // [B, QH, S, HD]
     const unsigned short* __restrict__ k,   // [B, KVH, Lmax, HD]
@@ -56,6 +55,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_prefill_kernel(
     int kv_offset,  // absolute position of q row 0 within the kv sequence
     float scale,
     int causal) {
+  constexpr int QR = QTILE;      // q rows per wave
   constexpr int NSET = QR / 16;  // 16-row MFMA row sets per wave
   const int bh = blockIdx.x;          // b * q_heads + qh
   const int b = bh / q_heads;
@@ -290,18 +290,7 @@ torch::Tensor attn_prefill_fused(
   auto stream = at::cuda::getCurrentCUDAStream();
   const float sc = (float)scale;
 
-  static const int kvt_env = [] {
-    const char* s = std::getenv("PETALS_PREFILL_KVT");
-    return s ? std::atoi(s) : 64;
-  }();
-  static const int qr_env = [] {
-    const char* s = std::getenv("PETALS_PREFILL_QROWS");
-    return s ? std::atoi(s) : 16;
-  }();
-  // QR=32 halves K/V staging + barriers per flop but needs >=8 row-tiles to
-  // fill the chip for short sequences; use it only when the grid stays large
-  const int qr = (qr_env == 32 && S >= 2 * WAVES * 32) ? 32 : 16;
-  dim3 grid(B * QH, (S + WAVES * qr - 1) / (WAVES * qr));
+  dim3 grid(B * QH, (S + WAVES * QTILE - 1) / (WAVES * QTILE));
 
   const float* alibi_p = nullptr;
   if (alibi_slopes.has_value() && alibi_slopes->defined() && alibi_slopes->numel() > 0) {
@@ -314,28 +303,15 @@ torch::Tensor attn_prefill_fused(
   const auto* vp = reinterpret_cast<const unsigned short*>(v.data_ptr());
   auto* op = reinterpret_cast<unsigned short*>(out.data_ptr());
 
-#define PF_LAUNCH(HDV, KVTV, AB, QRV)                                                       \
-  attn_prefill_kernel<HDV, KVTV, AB, QRV><<<grid, WAVES * WAVE, 0, stream>>>(               \
+#define PF_LAUNCH(HDV, AB)                                                                  \
+  attn_prefill_kernel<HDV, AB><<<grid, WAVES * WAVE, 0, stream>>>(                          \
       qp, kp, vp, op, alibi_p, QH, KVH, S, LMAX, (int)kv_len, (int)kv_offset, sc, causal ? 1 : 0)
-#define PF_QR(HDV, KVTV, AB)                                                                \
-  do {                                                                                      \
-    if (qr == 32) PF_LAUNCH(HDV, KVTV, AB, 32); else PF_LAUNCH(HDV, KVTV, AB, 16);          \
-  } while (0)
   const bool ab = alibi_p != nullptr;
   if (HD == 128) {
-    if (kvt_env == 32) {
-      if (ab) PF_QR(128, 32, true); else PF_QR(128, 32, false);
-    } else {
-      if (ab) PF_QR(128, 64, true); else PF_QR(128, 64, false);
-    }
+    if (ab) PF_LAUNCH(128, true); else PF_LAUNCH(128, false);
   } else {
-    if (kvt_env == 32) {
-      if (ab) PF_QR(64, 32, true); else PF_QR(64, 32, false);
-    } else {
-      if (ab) PF_QR(64, 64, true); else PF_QR(64, 64, false);
-    }
+    if (ab) PF_LAUNCH(64, true); else PF_LAUNCH(64, false);
   }
-#undef PF_QR
 #undef PF_LAUNCH
   HIP_CHECK_LAST();
   return out;

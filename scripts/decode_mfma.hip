@@ -1,6 +1,6 @@
 // Prototype: MFMA decode attention (flash-decoding) for CDNA4.
 //
-// The shipping attn_decode_kernel is VALU-bound: each cache row costs a
+// The VALU decode kernel this replaced was VALU-bound: each cache row cost a
 // 16-lane dot-product shuffle reduce per q head, capping at ~1.5 TB/s of
 // K/V traffic at kv=131k (profiles/decode_longctx_sweep.log). Here the GQ
 // query heads of one kv head form the rows of an mfma_f32_16x16x32_bf16

@@ -48,8 +48,6 @@ def run_case(name, b, qh, kvh, s, hd, off, causal):
         print(f"  worst head ({bb},{hh}): bad rows {bad[:40]}{'...' if len(bad) > 40 else ''} of {s}")
 
 
-kvt = os.environ.get("PETALS_PREFILL_KVT", "64(default)")
-print(f"KVT={kvt}")
 run_case("case0 b2 qh8 kvh2 s67 hd128 causal", 2, 8, 2, 67, 128, 0, True)
 run_case("case1 b1 qh4 kvh4 s200 hd128 causal", 1, 4, 4, 200, 128, 0, True)
 run_case("case2 b1 qh8 kvh8 s33 hd64 off50", 1, 8, 8, 33, 64, 50, True)

@@ -1,6 +1,6 @@
-"""Sharp numerics tests for the attention path: `attn_decode_fused` (MFMA and
-VALU kernels), `attn_prefill_fused`, and the decode-step cache writers that
-produce the rows the attention reads.
+"""Sharp numerics tests for the attention path: `attn_decode_fused`,
+`attn_prefill_fused`, and the decode-step cache writers that produce the rows
+the attention reads.
 
 How the checks are built (see also docs/KERNELS.md, "How attention numerics
 are tested"):
@@ -21,11 +21,7 @@ The CPU self-checks run without a GPU; GPU tests carry the `gpu` mark.
 
 import dataclasses
 import functools
-import json
 import math
-import os
-import subprocess
-import sys
 import zlib
 from typing import List, Optional, Tuple
 
@@ -926,51 +922,3 @@ def test_cache_writers_at_real_positions(hip, kernel, hd, pos):
     ]
     print(f"writer {kernel}-hd{hd}-pos{pos}: q_err={q_err:.2e} attn nerr={errs[0]:.5f} {errs[1]:.5f} tol={TOL_DECODE}")
     assert max(errs) <= TOL_DECODE, errs
-
-
-VALU_GROUPS = ("A", "B", "F")  # the VALU kernel does not support gq > 16
-
-
-def _valu_child():
-    """Runs in a fresh process with PETALS_DECODE_KERNEL=valu (the kernel choice
-    is latched per process): prints one JSON line per case."""
-    from petals_amd import ops
-
-    mod = ops._load_hip_ops()
-    assert mod is not None, repr(ops._hip_import_error)
-    for p in DECODE_PARAMS:
-        case, variant = p.values
-        if case.group in VALU_GROUPS:
-            e_big, e_nan = _decode_errors(mod, case, variant)
-            print(json.dumps({"id": p.id, "nerr": max(e_big, e_nan)}), flush=True)
-
-
-@pytest.mark.gpu
-@requires_gpu
-def test_attn_decode_valu_kernel():
-    """The VALU decode kernel (PETALS_DECODE_KERNEL=valu) on groups A, B, F."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PETALS_DECODE_KERNEL="valu")
-    env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
-    proc = subprocess.run(
-        [sys.executable, os.path.abspath(__file__), "--valu-child"],
-        env=env, cwd=root, capture_output=True, text=True, timeout=300,
-    )
-    assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
-    got = {}
-    for line in proc.stdout.splitlines():
-        if line.startswith("{"):
-            rec = json.loads(line)
-            got[rec["id"]] = rec["nerr"]
-    want = [p.id for p in DECODE_PARAMS if p.values[0].group in VALU_GROUPS]
-    assert sorted(got) == sorted(want)
-    for name in want:
-        print(f"valu {name}: nerr={got[name]:.5f} tol={TOL_DECODE}")
-    bad = {n: e for n, e in got.items() if not e <= TOL_DECODE}
-    assert not bad, bad
-
-
-if __name__ == "__main__":
-    if sys.argv[1:] == ["--valu-child"]:
-        assert os.environ.get("PETALS_DECODE_KERNEL") == "valu"
-        _valu_child()
