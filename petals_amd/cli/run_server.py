@@ -46,7 +46,7 @@ def _parse_size(s):
     return int(s) * mult
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="petals_amd server")
     parser.add_argument("model", nargs="?", default=None, help="model preset name or local checkpoint dir")
     parser.add_argument("--converted_model_name_or_path", default=None,
@@ -66,6 +66,9 @@ def main(argv=None):
     parser.add_argument("--prefill_gemm", type=str, default="dense", choices=["dense", "fused"],
                         help="prefill matmuls on quantized weights: rocBLAS on cached dequantized "
                              "copies (dense) or the dequant-fused MFMA GEMM (fused)")
+    parser.add_argument("--kv_cache_dtype", type=str, default="bf16", choices=["bf16", "fp8"],
+                        help="KV-cache element type: bf16, or fp8 (OCP E4M3, no scales; fused Llama / "
+                             "Mixtral blocks on one GPU) for half the cache bytes per token")
     parser.add_argument("--attn_cache_tokens", type=int, default=16384)
     parser.add_argument("--max_batch_size", type=int, default=8)
     parser.add_argument("--max_chunk_size_bytes", type=int, default=256 * 1024 * 1024,
@@ -113,6 +116,11 @@ def main(argv=None):
                              "run one process per rank under torchrun")
     for flag, why in _REJECTED_FLAGS.items():
         parser.add_argument(flag, default=None, help=f"NOT SUPPORTED: {why}")
+    return parser
+
+
+def main(argv=None):
+    parser = build_parser()
     args = parser.parse_args(argv)
 
     for flag, why in _REJECTED_FLAGS.items():
@@ -225,6 +233,7 @@ def main(argv=None):
         max_disk_space=_parse_size(args.max_disk_space),
         tensor_parallel_ranks=args.tensor_parallel_ranks,
         prefill_gemm=args.prefill_gemm,
+        kv_cache_dtype=args.kv_cache_dtype,
     )
     server.start()
     print(f"petals_amd server listening on {server.listen_addr} peer_id={server.peer_id}", flush=True)

@@ -166,6 +166,13 @@ def attention_decode(q, k_cache, v_cache, kv_len: int, *, attn_bias=None, scale=
             )
     k = k_cache[:, :, :kv_len]
     v = v_cache[:, :, :kv_len]
+    if k.dtype == torch.float8_e4m3fn:
+        # fp8 KV cache (ops/kv_fp8.py) on the torch composition: dequantize
+        # (exact) first, matmul is not defined for float8
+        from petals_amd.ops import kv_fp8
+
+        compute = q.dtype if q.dtype in (torch.bfloat16, torch.float32) else torch.float32
+        k, v = kv_fp8.dequantize(k, compute), kv_fp8.dequantize(v, compute)
     if alibi_slopes is not None and attn_bias is None:
         attn_bias = _alibi_bias_matrix(alibi_slopes, kv_len, q.device)
     return reference.attention(

@@ -38,11 +38,16 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 // L2/HBM and are negligible for the weight-bound decode shapes that need
 // GQ > 16 (falcon-7b MQA gq=71, falcon-180b gq=29 — reference
 // models/falcon/block.py:100-110).
-template <int HD, int GQ>
+//
+// FP8: the caches hold OCP E4M3 bytes (torch.float8_e4m3fn, no scales)
+// instead of bf16. Only the two global reads differ: the K B-fragment is 8
+// bytes per lane and V rows arrive as 8-byte chunks, both converted (exactly)
+// to the bf16x8 the bf16 instantiation loads. Everything downstream is shared.
+template <int HD, int GQ, bool FP8 = false>
 __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
     const float* __restrict__ q,            // [B, KV, GQ, HD]
-    const unsigned short* __restrict__ k_cache,  // [B, KV, lmax, HD]
-    const unsigned short* __restrict__ v_cache,
+    const typename std::conditional<FP8, unsigned char, unsigned short>::type* __restrict__ k_cache,  // [B, KV, lmax, HD]
+    const typename std::conditional<FP8, unsigned char, unsigned short>::type* __restrict__ v_cache,
     float* __restrict__ part_o,             // [B*KV, splits, GQ, HD]
     float* __restrict__ part_ml,            // [B*KV, splits, GQ, 2]
     const int* __restrict__ kv_len_ptr,
@@ -80,8 +85,8 @@ __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
   static_assert(16 * HD * 4 <= HD * (DKVT + DKPAD) * 2, "combine O overlay too big");
 
   const size_t kv_base = (size_t)bkv * lmax * HD;
-  const unsigned short* kb = k_cache + kv_base;
-  const unsigned short* vb = v_cache + kv_base;
+  const auto* kb = k_cache + kv_base;
+  const auto* vb = v_cache + kv_base;
   const size_t q_base = (size_t)bkv * GQ * HD;
 
   for (int a = 0; a < GA; ++a) {
@@ -132,7 +137,12 @@ __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
         const int row = idx / (HD / 8);
         const int c8 = (idx - row * (HD / 8)) * 8;
         bf16x8 vv8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (j0 + row < j_end) vv8 = *reinterpret_cast<const bf16x8*>(vb + (size_t)(j0 + row) * HD + c8);
+        if (j0 + row < j_end) {
+          if constexpr (FP8)
+            vv8 = e4m3x8_to_bf16x8(*reinterpret_cast<const uint2*>(vb + (size_t)(j0 + row) * HD + c8));
+          else
+            vv8 = *reinterpret_cast<const bf16x8*>(vb + (size_t)(j0 + row) * HD + c8);
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           *reinterpret_cast<unsigned short*>(&vt_raw[wave][DVT_BYTE(c8 + e, row * 2)]) = (unsigned short)vv8[e];
@@ -145,10 +155,14 @@ __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
       for (int nb = 0; nb < DKVT / 16; ++nb) {
         s_acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
         const int key = j0 + nb * 16 + col;
-        const unsigned short* krow = kb + (size_t)min(key, j_end - 1) * HD + hi * 8;
+        const auto* krow = kb + (size_t)min(key, j_end - 1) * HD + hi * 8;
 #pragma unroll
         for (int kc = 0; kc < KCH; ++kc) {
-          const bf16x8 kt = *reinterpret_cast<const bf16x8*>(krow + kc * 32);
+          bf16x8 kt;
+          if constexpr (FP8)
+            kt = e4m3x8_to_bf16x8(*reinterpret_cast<const uint2*>(krow + kc * 32));
+          else
+            kt = *reinterpret_cast<const bf16x8*>(krow + kc * 32);
           s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q_frag[kc], kt, s_acc[nb], 0, 0, 0);
         }
       }
@@ -280,7 +294,8 @@ __global__ void attn_decode_combine_kernel(
 
 // ---------------------------------------------------------------- host API
 
-// q: [B, KV*GQ*HD] f32 (token per row); caches [Bc, KV, Lmax, HD] bf16;
+// q: [B, KV*GQ*HD] f32 (token per row); caches [Bc, KV, Lmax, HD] bf16 or
+// float8_e4m3fn (both alike);
 // kv_len: device int32 scalar tensor. Returns [B, KV*GQ*HD] f32.
 torch::Tensor attn_decode_fused(
     torch::Tensor q,
@@ -294,8 +309,13 @@ torch::Tensor attn_decode_fused(
     double scale,
     c10::optional<torch::Tensor> alibi_slopes) {  // [kv_heads*GQ] f32
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kFloat32);
-  TORCH_CHECK(k_cache.dtype() == torch::kBFloat16 && k_cache.dim() == 4);
+  const bool fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK((fp8 || k_cache.scalar_type() == at::kBFloat16) && k_cache.dim() == 4,
+              "kv cache must be bf16 or float8_e4m3fn");
+  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type(), "k and v caches must share a dtype");
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes() && k_cache.is_contiguous() && v_cache.is_contiguous());
   const int b = q.size(0);
+  TORCH_CHECK(b <= k_cache.size(0), "more q rows than cache rows");
   const int kv_heads = k_cache.size(1), lmax = k_cache.size(2), hd = k_cache.size(3);
   const int GQi = (int)gq;
   int n_splits = (int)n_splits_i;
@@ -341,9 +361,15 @@ torch::Tensor attn_decode_fused(
   bool launched = false;
 #define ATTN_CASE(HDV, GQV)                                                   \
   if (hd == HDV && GQi == GQV) {                                              \
-    mfma_decode_kernel<HDV, GQV><<<grid, DWAVES * WAVE, 0, stream>>>(         \
-        qp, kp, vp, pop, pmlp, lenp, alibi_p, kv_heads, lmax, n_splits, sc,   \
-        direct_p);                                                            \
+    if (fp8)                                                                  \
+      mfma_decode_kernel<HDV, GQV, true><<<grid, DWAVES * WAVE, 0, stream>>>( \
+          qp, reinterpret_cast<const unsigned char*>(kp),                     \
+          reinterpret_cast<const unsigned char*>(vp), pop, pmlp, lenp,        \
+          alibi_p, kv_heads, lmax, n_splits, sc, direct_p);                   \
+    else                                                                      \
+      mfma_decode_kernel<HDV, GQV><<<grid, DWAVES * WAVE, 0, stream>>>(       \
+          qp, kp, vp, pop, pmlp, lenp, alibi_p, kv_heads, lmax, n_splits, sc, \
+          direct_p);                                                          \
     launched = true;                                                          \
   }
   ATTN_CASE(128, 1) ATTN_CASE(128, 2) ATTN_CASE(128, 4) ATTN_CASE(128, 6)

@@ -16,6 +16,7 @@ void rope_cache_write(
 void kv_cache_write(
     torch::Tensor qkv, torch::Tensor pos,
     torch::Tensor k_cache, torch::Tensor v_cache, int64_t qh, int64_t kh);
+void kv_cache_store_fp8(torch::Tensor new_kv, torch::Tensor cache, int64_t prefix_length);
 torch::Tensor qkv_rope_reduce(
     torch::Tensor partials, c10::optional<torch::Tensor> cos_t, c10::optional<torch::Tensor> sin_t,
     torch::Tensor pos, torch::Tensor k_cache, torch::Tensor v_cache,
@@ -81,6 +82,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("apply_rope", &apply_rope, "rotate q,k by positions (bf16)");
   m.def("rope_cache_write", &rope_cache_write, "fused decode rope + kv cache write");
   m.def("kv_cache_write", &kv_cache_write, "decode kv cache write without rope (ALiBi families)");
+  m.def("kv_cache_store_fp8", &kv_cache_store_fp8,
+        "prefill write bf16 [B, KV, S, hd] -> float8_e4m3fn cache rows [prefix, prefix+S) "
+        "(saturating, round to nearest even)",
+        py::arg("new_kv"), py::arg("cache"), py::arg("prefix_length"));
   m.def("qkv_rope_reduce", &qkv_rope_reduce,
         "fused qkv split-K reduce + rope + kv-cache write (consumes RAW gemv partials)",
         py::arg("partials"), py::arg("cos_t"), py::arg("sin_t"), py::arg("pos"),

@@ -368,17 +368,35 @@ std::vector<torch::Tensor> apply_rope(
   return {qc, kc};
 }
 
+// ------------------------------------------------ kv cache dtype checks
+
+// Decode-step cache pair: [bcap >= b, kh, lmax, hd], contiguous, both bf16 or
+// both float8_e4m3fn (OCP E4M3, no scales). Returns true for fp8.
+static bool check_kv_caches(const torch::Tensor& k_cache, const torch::Tensor& v_cache, int64_t b) {
+  const bool fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(k_cache.is_cuda() && k_cache.dim() == 4 && (fp8 || k_cache.scalar_type() == at::kBFloat16),
+              "kv cache must be a 4-d bf16 or float8_e4m3fn device tensor");
+  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type() && v_cache.sizes() == k_cache.sizes(),
+              "k and v caches must share dtype and shape");
+  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous() && b <= k_cache.size(0),
+              "kv caches must be contiguous and cover the batch");
+  return fp8;
+}
+
 // -------------------------- fused decode rope + kv-cache write (fast path)
 
 // qkv: [b, qh*hd + 2*kh*hd] f32 (one token per row). Rotates q in place,
-// rotates k and writes k/v into the caches (bf16) at row *pos_ptr.
+// rotates k and writes k/v into the caches at row *pos_ptr. CT is the cache
+// element: unsigned short (bf16) or unsigned char (OCP E4M3, the fp32 value
+// that bf16 would round is clamped to +-448 and rounded once, f32_to_kv).
+template <typename CT>
 __global__ void rope_cache_write_kernel(
     float* __restrict__ qkv,
     const float* __restrict__ cos_t,
     const float* __restrict__ sin_t,
     const int* __restrict__ pos_ptr,
-    unsigned short* __restrict__ k_cache,  // [bcap, kh, lmax, hd]
-    unsigned short* __restrict__ v_cache,
+    CT* __restrict__ k_cache,  // [bcap, kh, lmax, hd]
+    CT* __restrict__ v_cache,
     int b, int qh, int kh, int lmax, int hd) {
   const int half = hd / 2;
   const int p = *pos_ptr;
@@ -405,9 +423,9 @@ __global__ void rope_cache_write_kernel(
         const int kh_i = h - qh;
         float* base = qkv + (size_t)bi * row_elems + qh * hd + kh_i * hd;
         const float x1 = base[d], x2 = base[d + half];
-        unsigned short* krow = k_cache + (((size_t)bi * kh + kh_i) * lmax + p) * hd;
-        krow[d] = f32_to_bf16(x1 * c - x2 * s);
-        krow[d + half] = f32_to_bf16(x2 * c + x1 * s);
+        CT* krow = k_cache + (((size_t)bi * kh + kh_i) * lmax + p) * hd;
+        krow[d] = f32_to_kv<CT>(x1 * c - x2 * s);
+        krow[d + half] = f32_to_kv<CT>(x2 * c + x1 * s);
       }
     } else {
       long t = idx - rot_total;
@@ -415,7 +433,7 @@ __global__ void rope_cache_write_kernel(
       const int kh_i = t % kh; t /= kh;
       const int bi = t;
       const float v = qkv[(size_t)bi * row_elems + qh * hd + kh * hd + kh_i * hd + d];
-      v_cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + d] = f32_to_bf16(v);
+      v_cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + d] = f32_to_kv<CT>(v);
     }
   }
 }
@@ -431,7 +449,7 @@ __global__ void rope_cache_write_kernel(
 // halves each thread's serial split chain vs 8 — measured +0.9-1.0 tok/s on
 // every alternating pair (profiles/qrr_groups_ab.log)
 
-template <bool ROPE>
+template <bool ROPE, typename CT>
 __global__ __launch_bounds__(64 * QKV_RED_GROUPS) void qkv_rope_reduce_kernel(
     const float* __restrict__ partials,  // [splits, b, row_elems]
     const float* __restrict__ cos_t,     // [max_pos, hd]
@@ -439,8 +457,8 @@ __global__ __launch_bounds__(64 * QKV_RED_GROUPS) void qkv_rope_reduce_kernel(
     const int* __restrict__ pos_ptr,
     const unsigned short* __restrict__ bias,  // [row_elems] bf16 or null
     float* __restrict__ q_out,             // [b, qh*hd] f32 (rotated)
-    unsigned short* __restrict__ k_cache,  // [bcap, kh, lmax, hd]
-    unsigned short* __restrict__ v_cache,
+    CT* __restrict__ k_cache,              // [bcap, kh, lmax, hd] bf16 or e4m3
+    CT* __restrict__ v_cache,
     int n_splits, int b, int qh, int kh, int lmax, int hd) {
   constexpr int G = QKV_RED_GROUPS;
   __shared__ float acc_a[G][64];
@@ -498,12 +516,12 @@ __global__ __launch_bounds__(64 * QKV_RED_GROUPS) void qkv_rope_reduce_kernel(
     q_out[(size_t)bi * qh * hd + o] = val;
   } else if (in_k) {
     const int kh_i = (o - qh * hd) / hd;
-    k_cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + d] = f32_to_bf16(val);
+    k_cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + d] = f32_to_kv<CT>(val);
   } else {
     const int t = o - qh * hd - kh * hd;
     const int kh_i = t / hd;
     const int dv = t - kh_i * hd;
-    v_cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + dv] = f32_to_bf16(val);
+    v_cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + dv] = f32_to_kv<CT>(val);
   }
 }
 
@@ -517,6 +535,7 @@ torch::Tensor qkv_rope_reduce(
     int64_t qh, int64_t kh, bool rope,
     c10::optional<torch::Tensor> bias) {
   TORCH_CHECK(partials.is_cuda() && partials.dtype() == torch::kFloat32 && partials.dim() == 3);
+  const bool fp8 = check_kv_caches(k_cache, v_cache, partials.size(1));
   const int n_splits = partials.size(0);
   const int b = partials.size(1);
   const int kh_i = k_cache.size(1), lmax = k_cache.size(2), hd = k_cache.size(3);
@@ -539,26 +558,32 @@ torch::Tensor qkv_rope_reduce(
     TORCH_CHECK(bias->numel() == partials.size(2));
     bp = reinterpret_cast<const unsigned short*>(bias->data_ptr());
   }
-#define LAUNCH_QRR(R)                                                          \
-  qkv_rope_reduce_kernel<R><<<blocks, 64 * QKV_RED_GROUPS, 0, stream>>>(       \
+#define LAUNCH_QRR(R, CT)                                                      \
+  qkv_rope_reduce_kernel<R, CT><<<blocks, 64 * QKV_RED_GROUPS, 0, stream>>>(   \
       partials.data_ptr<float>(), cp, sp, pos.data_ptr<int>(), bp,             \
       q_out.data_ptr<float>(),                                                 \
-      reinterpret_cast<unsigned short*>(k_cache.data_ptr()),                   \
-      reinterpret_cast<unsigned short*>(v_cache.data_ptr()),                   \
+      reinterpret_cast<CT*>(k_cache.data_ptr()),                               \
+      reinterpret_cast<CT*>(v_cache.data_ptr()),                               \
       n_splits, b, (int)qh, (int)kh, lmax, hd)
-  if (rope) LAUNCH_QRR(true); else LAUNCH_QRR(false);
+  if (fp8) {
+    if (rope) LAUNCH_QRR(true, unsigned char); else LAUNCH_QRR(false, unsigned char);
+  } else {
+    if (rope) LAUNCH_QRR(true, unsigned short); else LAUNCH_QRR(false, unsigned short);
+  }
 #undef LAUNCH_QRR
   HIP_CHECK_LAST();
   return q_out;
 }
 
 // kv cache write WITHOUT rope for ALiBi families (BLOOM): same [q|k|v] fused
-// layout as rope_cache_write, k and v copied bf16 into the caches at *pos.
+// layout as rope_cache_write, k and v copied (bf16 or e4m3) into the caches at
+// *pos.
+template <typename CT>
 __global__ void kv_cache_write_kernel(
     const float* __restrict__ qkv,
     const int* __restrict__ pos_ptr,
-    unsigned short* __restrict__ k_cache,  // [bcap, kh, lmax, hd]
-    unsigned short* __restrict__ v_cache,
+    CT* __restrict__ k_cache,  // [bcap, kh, lmax, hd]
+    CT* __restrict__ v_cache,
     int b, int qh, int kh, int lmax, int hd) {
   const int p = *pos_ptr;
   const int row_elems = qh * hd + 2 * kh * hd;
@@ -571,8 +596,8 @@ __global__ void kv_cache_write_kernel(
     const int kh_i = t % kh; t /= kh;
     const int bi = t;
     const float val = qkv[(size_t)bi * row_elems + qh * hd + (is_v ? kh * hd : 0) + kh_i * hd + d];
-    unsigned short* cache = is_v ? v_cache : k_cache;
-    cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + d] = f32_to_bf16(val);
+    CT* cache = is_v ? v_cache : k_cache;
+    cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + d] = f32_to_kv<CT>(val);
   }
 }
 
@@ -580,17 +605,21 @@ void kv_cache_write(
     torch::Tensor qkv, torch::Tensor pos,
     torch::Tensor k_cache, torch::Tensor v_cache, int64_t qh, int64_t kh) {
   TORCH_CHECK(qkv.is_cuda() && qkv.dtype() == torch::kFloat32 && qkv.dim() == 2);
-  TORCH_CHECK(k_cache.dtype() == torch::kBFloat16 && k_cache.dim() == 4);
+  const bool fp8 = check_kv_caches(k_cache, v_cache, qkv.size(0));
   const int b = qkv.size(0);
   const int hd = k_cache.size(3), lmax = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(1) == kh && qkv.size(1) == (qh + 2 * kh) * hd, "qkv width mismatch");
   const long total = 2L * b * kh * hd;
   const long blocks = std::min((total + 255) / 256 + 1, (long)1024);
   auto stream = at::cuda::getCurrentCUDAStream();
-  kv_cache_write_kernel<<<blocks, 256, 0, stream>>>(
-      qkv.data_ptr<float>(), pos.data_ptr<int>(),
-      reinterpret_cast<unsigned short*>(k_cache.data_ptr()),
-      reinterpret_cast<unsigned short*>(v_cache.data_ptr()),
-      b, (int)qh, (int)kh, lmax, hd);
+#define LAUNCH_KVW(CT)                                                  \
+  kv_cache_write_kernel<CT><<<blocks, 256, 0, stream>>>(                \
+      qkv.data_ptr<float>(), pos.data_ptr<int>(),                       \
+      reinterpret_cast<CT*>(k_cache.data_ptr()),                        \
+      reinterpret_cast<CT*>(v_cache.data_ptr()),                        \
+      b, (int)qh, (int)kh, lmax, hd)
+  if (fp8) LAUNCH_KVW(unsigned char); else LAUNCH_KVW(unsigned short);
+#undef LAUNCH_KVW
   HIP_CHECK_LAST();
 }
 
@@ -598,17 +627,84 @@ void rope_cache_write(
     torch::Tensor qkv, torch::Tensor cos_t, torch::Tensor sin_t, torch::Tensor pos,
     torch::Tensor k_cache, torch::Tensor v_cache, int64_t qh, int64_t kh) {
   TORCH_CHECK(qkv.is_cuda() && qkv.dtype() == torch::kFloat32 && qkv.dim() == 2);
-  TORCH_CHECK(k_cache.dtype() == torch::kBFloat16 && k_cache.dim() == 4);
+  const bool fp8 = check_kv_caches(k_cache, v_cache, qkv.size(0));
   const int b = qkv.size(0);
   const int hd = k_cache.size(3), lmax = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(1) == kh && qkv.size(1) == (qh + 2 * kh) * hd, "qkv width mismatch");
   const long total = (long)b * (qh + kh) * (hd / 2) + (long)b * kh * hd;
   const long blocks = std::min((total + 255) / 256 + 1, (long)1024);
   auto stream = at::cuda::getCurrentCUDAStream();
-  rope_cache_write_kernel<<<blocks, 256, 0, stream>>>(
-      qkv.data_ptr<float>(), cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
-      pos.data_ptr<int>(),
-      reinterpret_cast<unsigned short*>(k_cache.data_ptr()),
-      reinterpret_cast<unsigned short*>(v_cache.data_ptr()),
-      b, (int)qh, (int)kh, lmax, hd);
+#define LAUNCH_RCW(CT)                                                          \
+  rope_cache_write_kernel<CT><<<blocks, 256, 0, stream>>>(                      \
+      qkv.data_ptr<float>(), cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),  \
+      pos.data_ptr<int>(),                                                      \
+      reinterpret_cast<CT*>(k_cache.data_ptr()),                                \
+      reinterpret_cast<CT*>(v_cache.data_ptr()),                                \
+      b, (int)qh, (int)kh, lmax, hd)
+  if (fp8) LAUNCH_RCW(unsigned char); else LAUNCH_RCW(unsigned short);
+#undef LAUNCH_RCW
+  HIP_CHECK_LAST();
+}
+
+// ------------------------------------------- prefill store into an fp8 cache
+// new_kv [B, KV, S, hd] bf16 -> cache[:B, :, prefix:prefix+S] as OCP E4M3 with
+// the decode writers' rounding (clamp to +-448, round to nearest even, NaN
+// kept). `copy_` is not usable here: torch's cast turns overflow into NaN.
+// One thread per 8 elements: one 16-byte load, four v_cvt_pk_fp8_f32, one
+// 8-byte store.
+__global__ void kv_cache_store_fp8_kernel(
+    const unsigned short* __restrict__ src,  // [b, kh, s, hd] bf16
+    unsigned char* __restrict__ cache,       // [bcap, kh, lmax, hd] e4m3
+    long n_chunks, int s_len, int lmax, int hd, int prefix) {
+  const int cpr = hd / 8;  // chunks per row
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < n_chunks;
+       idx += (long)gridDim.x * blockDim.x) {
+    const int c = idx % cpr;
+    const long row = idx / cpr;        // (b * kh) * s_len + s
+    const long bkh = row / s_len;
+    const int si = row - bkh * s_len;
+    const short8 v = *reinterpret_cast<const short8*>(src + idx * 8);
+    bool has_nan = false;
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const unsigned short u = (unsigned short)v[e];
+      has_nan |= (u & 0x7FFFu) > 0x7F80u;
+      f[e] = e4m3_clamp(bf16_to_f32(u));
+    }
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+    unsigned char* dst = cache + ((bkh * lmax + prefix + si) * hd + c * 8);
+    if (has_nan) {  // rare: per-element path keeps each NaN a NaN
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dst[e] = f32_to_e4m3(bf16_to_f32((unsigned short)v[e]));
+    } else {
+      *reinterpret_cast<uint2*>(dst) = make_uint2((unsigned)lo, (unsigned)hi);
+    }
+  }
+}
+
+void kv_cache_store_fp8(torch::Tensor new_kv, torch::Tensor cache, int64_t prefix_length) {
+  TORCH_CHECK(new_kv.is_cuda() && new_kv.scalar_type() == at::kBFloat16 && new_kv.dim() == 4,
+              "kv_cache_store_fp8 expects bf16 [B, KV, S, hd]");
+  TORCH_CHECK(cache.is_cuda() && cache.scalar_type() == at::kFloat8_e4m3fn && cache.dim() == 4 &&
+                  cache.is_contiguous(),
+              "kv_cache_store_fp8 expects a contiguous float8_e4m3fn cache");
+  const int64_t b = new_kv.size(0), kh = new_kv.size(1), s = new_kv.size(2), hd = new_kv.size(3);
+  TORCH_CHECK(b <= cache.size(0) && kh == cache.size(1) && hd == cache.size(3) && hd % 8 == 0,
+              "cache does not match new_kv");
+  TORCH_CHECK(prefix_length >= 0 && prefix_length + s <= cache.size(2), "write past the end of the cache");
+  if (new_kv.numel() == 0) return;
+  auto src = new_kv.contiguous();
+  const long n_chunks = src.numel() / 8;
+  const long blocks = std::min((n_chunks + 255) / 256, (long)4096);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  kv_cache_store_fp8_kernel<<<blocks, 256, 0, stream>>>(
+      reinterpret_cast<const unsigned short*>(src.data_ptr()),
+      reinterpret_cast<unsigned char*>(cache.data_ptr()),
+      n_chunks, (int)s, (int)cache.size(2), (int)hd, (int)prefix_length);
   HIP_CHECK_LAST();
 }

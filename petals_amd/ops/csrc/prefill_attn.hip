@@ -39,11 +39,16 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 // one K/V staging pass. NSET=2 (32 q rows per wave) lost its A/B
 // (profiles/prefill_qrows_ab.log) and is gone; the loop structure stays as it
 // was compiled, see the miscompile NOTE below before restructuring it.
-template <int HD, bool ALIBI>
+//
+// FP8: k / v hold OCP E4M3 bytes (torch.float8_e4m3fn KV cache, no scales).
+// Only the global -> LDS staging loop differs: it loads 8 bytes per chunk and
+// converts them (exactly) to the bf16x8 the bf16 instantiation loads; the LDS
+// images and everything after them are the same.
+template <int HD, bool ALIBI, bool FP8 = false>
 __global__ __launch_bounds__(WAVES * 64) void attn_prefill_kernel(
     const unsigned short* __restrict__ q,   // [B, QH, S, HD]
-    const unsigned short* __restrict__ k,   // [B, KVH, Lmax, HD]
-    const unsigned short* __restrict__ v,   // [B, KVH, Lmax, HD]
+    const typename std::conditional<FP8, unsigned char, unsigned short>::type* __restrict__ k,  // [B, KVH, Lmax, HD]
+    const typename std::conditional<FP8, unsigned char, unsigned short>::type* __restrict__ v,  // [B, KVH, Lmax, HD]
     unsigned short* __restrict__ out,       // [B, QH, S, HD]
     const float* __restrict__ alibi,        // [QH] ALiBi slopes or null (adds slope*key_abs;
                                             // the per-row constant cancels in softmax)
@@ -138,8 +143,13 @@ __global__ __launch_bounds__(WAVES * 64) void attn_prefill_kernel(
       bf16x8 kv8 = {0, 0, 0, 0, 0, 0, 0, 0};
       bf16x8 vv8 = {0, 0, 0, 0, 0, 0, 0, 0};
       if (j0 + row < kv_end) {
-        kv8 = *reinterpret_cast<const bf16x8*>(k + kv_base + (size_t)(j0 + row) * HD + c8);
-        vv8 = *reinterpret_cast<const bf16x8*>(v + kv_base + (size_t)(j0 + row) * HD + c8);
+        if constexpr (FP8) {
+          kv8 = e4m3x8_to_bf16x8(*reinterpret_cast<const uint2*>(k + kv_base + (size_t)(j0 + row) * HD + c8));
+          vv8 = e4m3x8_to_bf16x8(*reinterpret_cast<const uint2*>(v + kv_base + (size_t)(j0 + row) * HD + c8));
+        } else {
+          kv8 = *reinterpret_cast<const bf16x8*>(k + kv_base + (size_t)(j0 + row) * HD + c8);
+          vv8 = *reinterpret_cast<const bf16x8*>(v + kv_base + (size_t)(j0 + row) * HD + c8);
+        }
       }
       *reinterpret_cast<bf16x8*>(&k_lds[row][c8]) = kv8;
 #pragma unroll
@@ -280,9 +290,12 @@ torch::Tensor attn_prefill_fused(
     bool causal,
     c10::optional<torch::Tensor> alibi_slopes) {  // [QH] f32
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 4);
-  TORCH_CHECK(k.dtype() == torch::kBFloat16 && k.dim() == 4);
+  const bool fp8 = k.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK((fp8 || k.scalar_type() == at::kBFloat16) && k.dim() == 4, "k/v must be bf16 or float8_e4m3fn");
+  TORCH_CHECK(v.scalar_type() == k.scalar_type() && v.sizes() == k.sizes(), "k and v must share dtype and shape");
   const int B = q.size(0), QH = q.size(1), S = q.size(2), HD = q.size(3);
   const int KVH = k.size(1), LMAX = k.size(2);
+  TORCH_CHECK(k.size(0) >= B && k.size(3) == HD && kv_len <= LMAX, "k/v do not cover (batch, kv_len, head_dim)");
   TORCH_CHECK(HD == 128 || HD == 64, "prefill attention supports head_dim 64/128");
   TORCH_CHECK(QH % KVH == 0);
   TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
@@ -303,9 +316,15 @@ torch::Tensor attn_prefill_fused(
   const auto* vp = reinterpret_cast<const unsigned short*>(v.data_ptr());
   auto* op = reinterpret_cast<unsigned short*>(out.data_ptr());
 
+#define PF_ARGS op, alibi_p, QH, KVH, S, LMAX, (int)kv_len, (int)kv_offset, sc, causal ? 1 : 0
 #define PF_LAUNCH(HDV, AB)                                                                  \
-  attn_prefill_kernel<HDV, AB><<<grid, WAVES * WAVE, 0, stream>>>(                          \
-      qp, kp, vp, op, alibi_p, QH, KVH, S, LMAX, (int)kv_len, (int)kv_offset, sc, causal ? 1 : 0)
+  do {                                                                                      \
+    if (fp8)                                                                                \
+      attn_prefill_kernel<HDV, AB, true><<<grid, WAVES * WAVE, 0, stream>>>(                \
+          qp, reinterpret_cast<const unsigned char*>(kp), reinterpret_cast<const unsigned char*>(vp), PF_ARGS); \
+    else                                                                                    \
+      attn_prefill_kernel<HDV, AB><<<grid, WAVES * WAVE, 0, stream>>>(qp, kp, vp, PF_ARGS); \
+  } while (0)
   const bool ab = alibi_p != nullptr;
   if (HD == 128) {
     if (ab) PF_LAUNCH(128, true); else PF_LAUNCH(128, false);
@@ -313,6 +332,7 @@ torch::Tensor attn_prefill_fused(
     if (ab) PF_LAUNCH(64, true); else PF_LAUNCH(64, false);
   }
 #undef PF_LAUNCH
+#undef PF_ARGS
   HIP_CHECK_LAST();
   return out;
 }

@@ -637,8 +637,14 @@ class LlamaFastPath(_TPFastPathMixin):
         q, k = self.hip.apply_rope(q.contiguous(), k.contiguous(), self.rope_cos, self.rope_sin, pos)
         if kv_cache is not None:
             k_cache, v_cache = kv_cache
-            k_cache[:B, :, prefix_length:end].copy_(k)
-            v_cache[:B, :, prefix_length:end].copy_(v)
+            if k_cache.dtype == torch.float8_e4m3fn:
+                # fp8 cache (ops/kv_fp8.py): saturating store, since copy_'s
+                # cast turns overflow into NaN
+                self.hip.kv_cache_store_fp8(k, k_cache, prefix_length)
+                self.hip.kv_cache_store_fp8(v, v_cache, prefix_length)
+            else:
+                k_cache[:B, :, prefix_length:end].copy_(k)
+                v_cache[:B, :, prefix_length:end].copy_(v)
             attn = self.hip.attn_prefill_fused(
                 q.contiguous(), k_cache[:B].contiguous(), v_cache[:B].contiguous(),
                 end, prefix_length, self.scale, True,

@@ -30,6 +30,7 @@ class TransformerBackend:
         memory_cache: MemoryCache,
         dtype: torch.dtype,
         max_chunk_size_bytes: int = 256 * 1024 * 1024,
+        cache_dtype: Optional[torch.dtype] = None,
     ):
         self.uid = uid
         self.block = block
@@ -37,6 +38,10 @@ class TransformerBackend:
         self.memory_cache = memory_cache
         self.dtype = dtype
         self.dtype_bytes = get_size_in_bytes(dtype)
+        # KV-cache element type: the compute dtype, or torch.float8_e4m3fn for
+        # the opt-in fp8 cache (ops/kv_fp8.py; fused Llama/Mixtral blocks only,
+        # Server validates that)
+        self.cache_dtype = dtype if cache_dtype is None else cache_dtype
         self.max_chunk_size_bytes = max_chunk_size_bytes
         for p in block.parameters():
             p.requires_grad_(False)
@@ -47,7 +52,14 @@ class TransformerBackend:
 
     def get_inference_cache_descriptors(self, batch_size: int, max_length: int) -> Sequence[TensorDescriptor]:
         k_shape, v_shape = self.block.kv_cache_shape(batch_size, max_length)
-        return [TensorDescriptor(k_shape, self.dtype), TensorDescriptor(v_shape, self.dtype)]
+        return [TensorDescriptor(k_shape, self.cache_dtype), TensorDescriptor(v_shape, self.cache_dtype)]
+
+    @property
+    def kv_cache_dtype_name(self) -> str:
+        """`fp8` for the float8_e4m3fn cache, else the compute dtype's name."""
+        if self.cache_dtype == torch.float8_e4m3fn:
+            return "fp8"
+        return {torch.bfloat16: "bf16"}.get(self.cache_dtype, str(self.cache_dtype).replace("torch.", ""))
 
     def cache_bytes_per_token(self, batch_size: int = 1) -> int:
         descs = self.get_inference_cache_descriptors(batch_size, 1)
@@ -69,8 +81,11 @@ class TransformerBackend:
             k_cache, v_cache = cache_tensors
             if hypo_ids is not None and not is_dummy(hypo_ids):
                 hypo_ids = hypo_ids.to(k_cache.device)
-                k_cache[...] = k_cache[hypo_ids]
-                v_cache[...] = v_cache[hypo_ids]
+                from petals_amd.ops import kv_fp8
+
+                # fp8 rows move byte-exactly (through a uint8 view)
+                k_cache[...] = kv_fp8.index_rows(k_cache, hypo_ids)
+                v_cache[...] = kv_fp8.index_rows(v_cache, hypo_ids)
             max_chunk = self._estimate_max_chunk_length(hidden_states, prefix_length)
             if seq_len <= max_chunk:
                 out = self.block(hidden_states, kv_cache=(k_cache, v_cache), prefix_length=prefix_length)
@@ -131,6 +146,7 @@ class TransformerBackend:
             "uid": self.uid,
             "hidden_size": self.config.hidden_size,
             "dtype": str(self.dtype).replace("torch.", ""),
+            "kv_cache_dtype": self.kv_cache_dtype_name,
             "device": str(self.device),
         }
 

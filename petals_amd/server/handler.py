@@ -180,6 +180,7 @@ class TransformerConnectionHandler:
             "dht_client_mode": False,
             "cache_tokens_left": int(cache_bytes_left // max(1, bytes_per_token)),
             "adapters": list(self.adapters),
+            "kv_cache_dtype": first.kv_cache_dtype_name if first is not None else None,
             **self.server_info_extra(),
         }
         await stream.close(RpcMessage(meta=info))
@@ -382,8 +383,10 @@ class TransformerConnectionHandler:
             if has_hypo:
                 hypo = hypo_ids.to(device)
                 with self.memory_cache.use_cache(*(h for pair in handles for h in pair)) as tensors:
+                    from petals_amd.ops import kv_fp8
+
                     for t in tensors:
-                        t[...] = t[hypo]
+                        t[...] = kv_fp8.index_rows(t, hypo)  # fp8 rows move byte-exactly
             if session.span_graph is None:
                 cache_pairs = []
                 with self.memory_cache.use_cache(*(h for pair in handles for h in pair)) as tensors:

@@ -85,6 +85,7 @@ class Server:
         tensor_parallel_ranks: int = 1,
         tp_group=None,
         prefill_gemm: str = "dense",
+        kv_cache_dtype: str = "bf16",
     ):
         self.config = load_model_config(model_name_or_dir)
         self.model_name_or_dir = model_name_or_dir
@@ -103,6 +104,15 @@ class Server:
             dtype = torch.bfloat16 if self.device.type == "cuda" else torch.float32
         self.torch_dtype = dtype
         self.quant_type = quant_type
+        # intra-server tensor parallelism (parallel/tp.py): this process is one
+        # of `tensor_parallel_ranks` ranks sharding every served block
+        self.tensor_parallel_ranks = int(tensor_parallel_ranks)
+        self.tp_group = tp_group
+        # KV-cache element type: "bf16" keeps the compute dtype; "fp8" stores
+        # OCP E4M3 bytes without scales (ops/kv_fp8.py), halving the cache
+        # term of the block count and of the MemoryCache budget
+        self.kv_cache_dtype = kv_cache_dtype
+        self.cache_torch_dtype = self._resolve_kv_cache_dtype(kv_cache_dtype)
 
         self.block_indices: Optional[List[int]] = None
         if block_indices is not None:
@@ -160,10 +170,6 @@ class Server:
         self.stats_report_interval = stats_report_interval
         self.cache_dir = cache_dir
         self.max_disk_space = max_disk_space
-        # intra-server tensor parallelism (parallel/tp.py): this process is one
-        # of `tensor_parallel_ranks` ranks sharding every served block
-        self.tensor_parallel_ranks = int(tensor_parallel_ranks)
-        self.tp_group = tp_group
         # prefill matmuls on quantized weights: "fused" opts this PROCESS into
         # the dequant-fused MFMA GEMM (ops/csrc/gemm_quant.hip); "dense" leaves
         # the process setting (PETALS_AMD_PREFILL_GEMM, default dense) alone
@@ -176,6 +182,37 @@ class Server:
             set_prefill_gemm_mode("fused")
 
     # -------------------------------------------------------------- sizing
+
+    def _resolve_kv_cache_dtype(self, kv_cache_dtype: str) -> torch.dtype:
+        """`bf16` -> the compute dtype (unchanged behaviour); `fp8` ->
+        torch.float8_e4m3fn, which only the fused Llama / Mixtral fast paths on
+        a single GPU read and write."""
+        from petals_amd.ops import kv_fp8
+
+        dtype = kv_fp8.cache_dtype(kv_cache_dtype)  # ValueError on an unknown name
+        if kv_cache_dtype != "fp8":
+            return self.torch_dtype
+        cfg = self.config
+        if self.device.type != "cuda":
+            raise ValueError("kv_cache_dtype='fp8' needs a GPU: the CPU blocks keep a bf16/fp32 cache")
+        if cfg.model_type not in ("llama", "mixtral"):
+            raise ValueError(
+                f"kv_cache_dtype='fp8' is implemented for the Llama and Mixtral fast paths, not {cfg.model_type!r}"
+            )
+        if self.tensor_parallel_ranks != 1:
+            raise ValueError("kv_cache_dtype='fp8' is not implemented for tensor-parallel shards")
+        gq = cfg.num_attention_heads // cfg.n_kv_heads
+        if (
+            cfg.head_dim not in (64, 128)
+            or gq not in (1, 2, 4, 6, 8, 16)
+            or getattr(cfg, "attention_bias", False)
+            or getattr(cfg, "mlp_bias", False)
+        ):
+            raise ValueError(
+                "kv_cache_dtype='fp8' needs the fused fast path (head_dim 64/128, GQA group in "
+                "1/2/4/6/8/16, no projection biases); this geometry is served by the generic ops"
+            )
+        return dtype
 
     def _block_param_bytes(self) -> int:
         cfg = self.config
@@ -202,7 +239,8 @@ class Server:
             total = 16 << 30
         block_bytes = self._block_param_bytes()
         cache_bytes_per_block = (
-            2 * self.config.n_kv_heads * self.config.head_dim * attn_cache_tokens * get_size_in_bytes(self.torch_dtype)
+            2 * self.config.n_kv_heads * self.config.head_dim * attn_cache_tokens
+            * get_size_in_bytes(self.cache_torch_dtype)
         )
         autograd_reserve = 2 << 30
         usable = total * 0.92 - autograd_reserve
@@ -342,7 +380,7 @@ class Server:
             * self.config.n_kv_heads
             * self.config.head_dim
             * self.attn_cache_tokens
-            * get_size_in_bytes(self.torch_dtype)
+            * get_size_in_bytes(self.cache_torch_dtype)
             * len(block_indices)
         )
         self.memory_cache = MemoryCache(cache_bytes, self.device, alloc_timeout=self.max_alloc_timeout)
@@ -390,7 +428,7 @@ class Server:
                     add_adapter_to_block(block, ad)
             self.backends[uid] = TransformerBackend(
                 uid, block, config=self.config, memory_cache=self.memory_cache, dtype=self.torch_dtype,
-                max_chunk_size_bytes=self.max_chunk_size_bytes,
+                max_chunk_size_bytes=self.max_chunk_size_bytes, cache_dtype=self.cache_torch_dtype,
             )
 
         self.handler = TransformerConnectionHandler(

@@ -17,6 +17,7 @@ DTYPE_BYTES = {
     torch.float16: 2,
     torch.bfloat16: 2,
     torch.int8: 1,
+    torch.float8_e4m3fn: 1,  # opt-in fp8 KV cache (ops/kv_fp8.py)
     torch.uint8: 1,
     torch.int64: 8,
     torch.bool: 1,
