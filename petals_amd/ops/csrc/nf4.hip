@@ -232,6 +232,193 @@ __global__ __launch_bounds__(WAVE) void gemv_nf4_kernel(
   }
 }
 
+// ----------------------------------------- NF4 gemv, K split inside the workgroup
+
+// Same inner loop, pair LUT, per-lane layout AND the same arithmetic as
+// gemv_nf4_kernel followed by the reduce: for a split count S the K chunks are
+// the one-wave kernel's chunks, and the result is bit for bit what that kernel
+// and gemv_reduce_kernel / qkv_rope_reduce_kernel give for S splits.
+//
+// Both reduces sum the S partials in 16 groups, group g taking chunks g, g+16,
+// g+32, ... in that order, then add the 16 group sums. Here workgroup
+// blockIdx.y = g IS group g: wave w runs chunk g + 16 w, the waves park their
+// accumulators in LDS, and after one barrier they are added in the order the
+// reduce uses inside a group (see the combine below). The workgroup writes the group's sum
+// as its one partial row, so the reduce finds min(S, 16) rows instead of S,
+// one per group, and only adds the groups. Partial bytes fall by S / 16, the
+// LUT is built once per WAVES chunks, and no result changes by one bit.
+//
+// Every thread reaches both barriers: lanes past out_dim and waves whose chunk
+// index is past S run zero iterations and contribute +0. NT selects
+// non-temporal loads for the packed weight words only (each is read once per
+// token); absmax_t and x keep the default policy.
+//
+// LDS: 2 KB LUT + WAVES * BATCH * 2 KB combine buffer. WAVES 16 exists for
+// BATCH <= 3 only: at 1024 threads a wave has 128 VGPRs and BATCH 4 needs 200.
+// No instantiation uses scratch.
+#define NF4_RED_GROUPS 16  // = GEMV_REDUCE_GROUPS = QKV_RED_GROUPS (elementwise.hip)
+static_assert(NF4_RED_GROUPS == GEMV_REDUCE_GROUPS, "the wg kernel mirrors the reduce's grouping");
+template <int BATCH, int WAVES, bool NT>
+__global__ __launch_bounds__(WAVE * WAVES) void gemv_nf4_wg_kernel(
+    const unsigned char* __restrict__ packed,     // [in, out/2]
+    const unsigned short* __restrict__ absmax,    // [in, out/64]
+    const unsigned short* __restrict__ absmax_t,  // [out/64, in] or null
+    const float* __restrict__ x,                  // [BATCH, in] f32
+    float* __restrict__ partials,                 // [n_splits, BATCH, out]
+    int in_dim,
+    int out_dim,
+    int i_per_split,  // rows per chunk, multiple of 16 (the one-wave kernel's i_per_split)
+    int n_splits) {   // S, at most NF4_RED_GROUPS * WAVES
+  constexpr int OPL = NF4_OPL;
+  constexpr int UNROLL = 16;
+  constexpr int THREADS = WAVE * WAVES;
+  __shared__ float2 lut2[256];
+  __shared__ float comb[WAVES][BATCH][NF4_OUT_PER_WAVE];
+  for (int i = threadIdx.x; i < 256; i += THREADS)
+    lut2[i] = make_float2(NF4_LUT_C[i & 0xF], NF4_LUT_C[i >> 4]);
+  __syncthreads();
+
+  const int lane = threadIdx.x & (WAVE - 1);
+  // wave-uniform by construction; readfirstlane tells the compiler so, which
+  // keeps the x and absmax_t addresses scalar as in the one-wave kernel
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int out0 = blockIdx.x * (WAVE * OPL) + lane * OPL;
+  const int split = blockIdx.y;  // the reduce group this workgroup stands for
+  const int chunk = split + NF4_RED_GROUPS * wave;
+  // a wave past the last chunk gets an empty range
+  const int i_begin = chunk < n_splits ? chunk * i_per_split : in_dim;
+  const int i_end = min(i_begin + i_per_split, in_dim);
+  const bool live = out0 < out_dim;
+  const bool full = (out0 + OPL) <= out_dim;
+
+  float acc[BATCH][OPL];
+#pragma unroll
+  for (int b = 0; b < BATCH; ++b)
+#pragma unroll
+    for (int v = 0; v < OPL; ++v) acc[b][v] = 0.f;
+
+  if (full) {
+    const int half_out = out_dim >> 1;
+    const unsigned char* pp = packed + (size_t)i_begin * half_out + (out0 >> 1);
+    const unsigned short* amt = absmax_t ? absmax_t + (size_t)(out0 >> 6) * in_dim : nullptr;
+    int i = i_begin;
+    for (; i + UNROLL <= i_end; i += UNROLL) {
+      unsigned int pk[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const unsigned int* wp = reinterpret_cast<const unsigned int*>(pp + (size_t)u * half_out);
+        pk[u] = NT ? __builtin_nontemporal_load(wp) : *wp;
+      }
+      float am[UNROLL];
+      if (amt) {
+#pragma unroll
+        for (int c8 = 0; c8 < UNROLL / 8; ++c8) {
+          const short8 a8 = *reinterpret_cast<const short8*>(amt + i + c8 * 8);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) am[c8 * 8 + e] = bf16_to_f32((unsigned short)a8[e]);
+        }
+      } else {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u)
+          am[u] = bf16_to_f32(absmax[(size_t)(i + u) * (out_dim >> 6) + (out0 >> 6)]);
+      }
+      float xs[BATCH][UNROLL];
+#pragma unroll
+      for (int b = 0; b < BATCH; ++b)
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u)
+          xs[b][u] = x[(size_t)b * in_dim + i + u];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        float wf[OPL];
+#pragma unroll
+        for (int p2 = 0; p2 < 4; ++p2) {
+          const float2 w2 = lut2[(pk[u] >> (8 * p2)) & 0xFFu];
+          wf[2 * p2] = w2.x;
+          wf[2 * p2 + 1] = w2.y;
+        }
+#pragma unroll
+        for (int b = 0; b < BATCH; ++b) {
+          const float xa = xs[b][u] * am[u];
+#pragma unroll
+          for (int v = 0; v < OPL; ++v) acc[b][v] = fmaf(wf[v], xa, acc[b][v]);
+        }
+      }
+      pp += (size_t)UNROLL * half_out;
+    }
+    for (; i < i_end; ++i) {
+      const float am = bf16_to_f32(absmax[(size_t)i * (out_dim >> 6) + (out0 >> 6)]);
+#pragma unroll
+      for (int b = 0; b < BATCH; ++b) {
+        const float xa = x[(size_t)b * in_dim + i] * am;
+        const unsigned int wd =
+            *reinterpret_cast<const unsigned int*>(packed + (size_t)i * half_out + (out0 >> 1));
+#pragma unroll
+        for (int p2 = 0; p2 < 4; ++p2) {
+          const float2 w2 = lut2[(wd >> (8 * p2)) & 0xFFu];
+          acc[b][2 * p2] = fmaf(w2.x, xa, acc[b][2 * p2]);
+          acc[b][2 * p2 + 1] = fmaf(w2.y, xa, acc[b][2 * p2 + 1]);
+        }
+      }
+    }
+  } else if (live) {
+    for (int i = i_begin; i < i_end; ++i) {
+      const float am = bf16_to_f32(absmax[(size_t)i * (out_dim >> 6) + (out0 >> 6)]);
+#pragma unroll
+      for (int b = 0; b < BATCH; ++b) {
+        const float xa = x[(size_t)b * in_dim + i] * am;
+        // compile-time trip count with a guard, as in gemv_nf4_kernel: a
+        // runtime-bounded loop would put acc[][] on the scratch stack
+#pragma unroll
+        for (int v = 0; v < OPL; ++v) {
+          if (out0 + v < out_dim) {
+            const unsigned char byte = packed[(size_t)i * (out_dim >> 1) + ((out0 + v) >> 1)];
+            const float2 w2 = lut2[byte];
+            acc[b][v] = fmaf(((out0 + v) & 1) ? w2.y : w2.x, xa, acc[b][v]);
+          }
+        }
+      }
+    }
+  }
+
+  // combine: every wave parks its accumulators, then all threads sum over the
+  // waves in index order and write the workgroup's one partial row
+#pragma unroll
+  for (int b = 0; b < BATCH; ++b)
+#pragma unroll
+    for (int q = 0; q < OPL / 4; ++q)
+      reinterpret_cast<float4v*>(&comb[wave][b][lane * OPL])[q] =
+          float4v{acc[b][4 * q], acc[b][4 * q + 1], acc[b][4 * q + 2], acc[b][4 * q + 3]};
+  __syncthreads();
+  const int col0 = blockIdx.x * NF4_OUT_PER_WAVE;
+  // The group sum exactly as gemv_reduce_kernel and qkv_rope_reduce_kernel
+  // compute it over this group's m partials. Under -ffast-math their split
+  // loop `for (s = g; s < S; s += 16) a += p[s]` compiles to two interleaved
+  // accumulators (even and odd members, one packed add per pair), their sum,
+  // and then a scalar remainder for an odd last member; the order below is
+  // that one. __fadd_rn keeps fast-math from reassociating it here.
+  // tests/test_nf4_gemv_wg.py::test_bit_identical_to_one_wave_kernel holds the
+  // two in step: it fails if a compiler changes either side.
+  const int m = (n_splits - split + NF4_RED_GROUPS - 1) / NF4_RED_GROUPS;  // 1..WAVES
+#pragma unroll
+  for (int e = threadIdx.x; e < BATCH * NF4_OUT_PER_WAVE; e += THREADS) {
+    const int b = e / NF4_OUT_PER_WAVE;
+    const int c = e % NF4_OUT_PER_WAVE;
+    float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int w = 0; w + 1 < WAVES; w += 2) {
+      if (w + 1 < m) {
+        a0 = __fadd_rn(a0, comb[w][b][c]);
+        a1 = __fadd_rn(a1, comb[w + 1][b][c]);
+      }
+    }
+    float s = __fadd_rn(a0, a1);
+    if (m & 1) s = __fadd_rn(comb[m - 1][b][c], s);
+    if (col0 + c < out_dim)
+      partials[((size_t)split * BATCH + b) * out_dim + col0 + c] = s;
+  }
+}
+
 // ------------------------------------------------------------------- host
 
 std::vector<torch::Tensor> nf4_quantize(torch::Tensor w) {
@@ -277,13 +464,18 @@ torch::Tensor gemv_nf4(
     int64_t epilogue,
     int64_t splits_override,
     c10::optional<torch::Tensor> bias,        // [out] bf16, added pre-activation
-    c10::optional<torch::Tensor> absmax_t) {  // [out/64, in] bf16 (transposed copy)
+    c10::optional<torch::Tensor> absmax_t,    // [out/64, in] bf16 (transposed copy)
+    int64_t wg_waves,  // 0 or 1: gemv_nf4_kernel; 4, 8 or 16: gemv_nf4_wg_kernel where it fits
+    bool nt) {         // non-temporal packed-weight loads (gemv_nf4_wg_kernel only)
   TORCH_CHECK(packed.is_cuda() && packed.dtype() == torch::kUInt8);
   TORCH_CHECK(x.dtype() == torch::kFloat32 && x.dim() == 2);
   const int in_dim = packed.size(0);
   const int out_dim = packed.size(1) * 2;
   const int batch = x.size(0);
   TORCH_CHECK(x.size(1) == in_dim && batch <= 8, "NF4 decode gemv supports batch <= 8");
+  TORCH_CHECK(wg_waves == 0 || wg_waves == 1 || wg_waves == 4 || wg_waves == 8 || wg_waves == 16,
+              "wg_waves must be 0, 1, 4, 8 or 16");
+  TORCH_CHECK(!nt || wg_waves > 1, "nt selects a load policy of the wg kernel: give wg_waves 4, 8 or 16");
 
   const long out_waves = (out_dim + (long)NF4_OUT_PER_WAVE - 1) / NF4_OUT_PER_WAVE;
   // NF4 matrices are 4x smaller than bf16: allow chunks down to 64 input rows
@@ -296,6 +488,14 @@ torch::Tensor gemv_nf4(
   // gain (an unaligned split count put up to a third of rows on the slow path)
   const int i_per_split = (int)(((in_dim + splits - 1) / splits + 15L) & ~15L);
   splits = (in_dim + i_per_split - 1) / i_per_split;
+  // The wg kernel computes the same bits from the same chunks, one workgroup
+  // per reduce group. It runs when its waves cover every chunk of a group;
+  // otherwise (more chunks, batch 5..8, or 16 waves at batch 4, which has no
+  // instantiation) the one-wave kernel does, with the same result.
+  const int waves = (wg_waves > 1 && batch <= 4 && splits <= NF4_RED_GROUPS * wg_waves
+                     && !(wg_waves == 16 && batch == 4)) ? (int)wg_waves : 1;
+  const int n_chunks = (int)splits;       // K chunks
+  if (waves > 1 && splits > NF4_RED_GROUPS) splits = NF4_RED_GROUPS;  // partial rows written
 
   torch::Tensor partials;
   auto f32opts = x.options().dtype(torch::kFloat32);
@@ -320,10 +520,35 @@ torch::Tensor gemv_nf4(
         reinterpret_cast<const unsigned short*>(absmax.data_ptr()), amt_p,    \
         x.data_ptr<float>(), partials.data_ptr<float>(), in_dim, out_dim, i_per_split); \
     break;
-  switch (batch) {
-    LAUNCH_NF4(1) LAUNCH_NF4(2) LAUNCH_NF4(3) LAUNCH_NF4(4)
-    LAUNCH_NF4(5) LAUNCH_NF4(6) LAUNCH_NF4(7) LAUNCH_NF4(8)
+#define LAUNCH_NF4_WG(B, W, N)                                                \
+  gemv_nf4_wg_kernel<B, W, N><<<grid, WAVE * W, 0, stream>>>(                 \
+      packed.data_ptr<unsigned char>(),                                       \
+      reinterpret_cast<const unsigned short*>(absmax.data_ptr()), amt_p,      \
+      x.data_ptr<float>(), partials.data_ptr<float>(), in_dim, out_dim, i_per_split, n_chunks)
+#define LAUNCH_NF4_WG_W(B, W) \
+  do { if (nt) LAUNCH_NF4_WG(B, W, true); else LAUNCH_NF4_WG(B, W, false); } while (0)
+#define LAUNCH_NF4_WG_B(B)                                                    \
+  case B:                                                                     \
+    if (waves == 4) LAUNCH_NF4_WG_W(B, 4);                                    \
+    else if (waves == 8) LAUNCH_NF4_WG_W(B, 8);                               \
+    else LAUNCH_NF4_WG_W(B, 16);                                              \
+    break;
+  if (waves > 1) {
+    switch (batch) {
+      LAUNCH_NF4_WG_B(1) LAUNCH_NF4_WG_B(2) LAUNCH_NF4_WG_B(3)
+      case 4:
+        if (waves == 4) LAUNCH_NF4_WG_W(4, 4); else LAUNCH_NF4_WG_W(4, 8);
+        break;
+    }
+  } else {
+    switch (batch) {
+      LAUNCH_NF4(1) LAUNCH_NF4(2) LAUNCH_NF4(3) LAUNCH_NF4(4)
+      LAUNCH_NF4(5) LAUNCH_NF4(6) LAUNCH_NF4(7) LAUNCH_NF4(8)
+    }
   }
+#undef LAUNCH_NF4_WG_W
+#undef LAUNCH_NF4_WG_B
+#undef LAUNCH_NF4_WG
 #undef LAUNCH_NF4
   HIP_CHECK_LAST();
 

@@ -79,7 +79,13 @@ class DecodeContext:
         self.kv_len.add_(1)
 
 
-_split_autotune_cache: Dict[Tuple[str, int, int], int] = {}
+# (quant, in, out) -> tuned split count; for NF4 a (wg_waves, splits, nt) tuple
+_split_autotune_cache: Dict[Tuple[str, int, int], object] = {}
+_COLD_FLUSH_BYTES = 512 << 20  # twice the 256 MiB Infinity Cache
+_COLD_ROUNDS = 15
+# _FastWeight runs the NF4 wg kernel at the batch its policy was timed at; the
+# one-wave kernel gives the same bits at any batch, so larger batches keep it.
+_NF4_WG_MAX_BATCH = 1
 
 _PREFILL_GEMM_MODES = ("dense", "fused")
 
@@ -137,6 +143,8 @@ class _FastWeight:
     (profiles/gemv_split_sweep.log shows the optimum varies ~2x by shape);
     the result is cached process-wide so only the first block pays."""
 
+    wg_waves, nt = 0, False  # NF4 tuning beyond the split count (see __init__)
+
     def __init__(self, t_bf16: torch.Tensor, hip, quant: str):
         self.hip = hip
         self.quant = quant
@@ -163,9 +171,12 @@ class _FastWeight:
             self.scale8 = scale.to(torch.bfloat16).contiguous()
         else:
             self.t = t_bf16.contiguous()
-        self.splits = self._autotune(t_bf16.device)
+        tuned = self._autotune(t_bf16.device)
+        # NF4 tunes (wg_waves, splits, nt): the K split as for every format, then
+        # which kernel sums it and with which weight-load policy (same bits all)
+        self.wg_waves, self.splits, self.nt = tuned if isinstance(tuned, tuple) else (0, tuned, False)
 
-    def _autotune(self, device) -> int:
+    def _autotune(self, device):
         key = (self.quant, self.in_dim, self.out_dim)
         if key in _split_autotune_cache:
             return _split_autotune_cache[key]
@@ -204,8 +215,54 @@ class _FastWeight:
                 continue
             if dt < best_t:
                 best, best_t = s, dt
+        if self.quant == "nf4":
+            best = self._autotune_nf4_policy(device, best)
         _split_autotune_cache[key] = best
         return best
+
+    def _autotune_nf4_policy(self, device, splits: int) -> Tuple[int, int, bool]:
+        """For the split count the loop above chose, pick which NF4 kernel runs
+        it and how it loads weights: (wg_waves, splits, nt) among the one-wave
+        kernel and the wg kernel at 4, 8 and 16 waves with nt off and on.
+
+        The split count fixes the arithmetic: every candidate here returns the
+        same bits (gemv_nf4_wg_kernel mirrors the reduce's grouping), so this
+        choice can follow timings without changing a result. It is timed from
+        cold caches, because load policies rank the other way round on a weight
+        that sits in the 256 MiB Infinity Cache, and in decode no weight does:
+        every timed call follows a read pass over 512 MiB, has its own event
+        pair, candidates go round-robin for 15 rounds and medians decide. Paid
+        once per shape per process: 7 candidates x 15 rounds x ~0.5 ms, under
+        0.1 s. NF4 only; the other formats have one kernel and one policy."""
+        candidates = [(0, splits, False)]
+        for waves in (4, 8, 16):
+            candidates += [(waves, splits, False), (waves, splits, True)]
+        x = torch.randn(1, self.in_dim, device=device)
+        ws = _get_ws(device, "gemv", 64 * max(self.out_dim, 1))
+        flush = torch.zeros(_COLD_FLUSH_BYTES // 4, dtype=torch.int32, device=device)
+
+        def run(cand):
+            waves, s, nt = cand
+            return self.hip.gemv_nf4(self.packed, self.absmax, x, ws, None, 0, s, None, self.absmax_t, waves, nt)
+
+        def cold_call(cand):
+            flush.sum()  # read-only, like the weights that go by between two visits in decode
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            run(cand)
+            t1.record()
+            t1.synchronize()
+            return t0.elapsed_time(t1)
+
+        for cand in candidates:  # warm: code object, allocator
+            run(cand)
+        # round-robin, so clock and thermal drift hits every candidate alike
+        times = {cand: [] for cand in candidates}
+        for _ in range(_COLD_ROUNDS):
+            for cand in candidates:
+                times[cand].append(cold_call(cand))
+        med = {cand: sorted(t)[len(t) // 2] for cand, t in times.items()}
+        return min(med, key=med.get)
 
     @property
     def shape(self):
@@ -222,6 +279,9 @@ class _FastWeight:
         return self.hip.gemv_bf16(self.t, x, ws, residual, epilogue, splits, bias)
 
     def gemv(self, x, ws, residual, epilogue, bias=None):
+        if self.quant == "nf4" and self.wg_waves > 1 and x.shape[0] <= _NF4_WG_MAX_BATCH:
+            return self.hip.gemv_nf4(self.packed, self.absmax, x, ws, residual, epilogue, self.splits, bias,
+                                     self.absmax_t, self.wg_waves, self.nt)
         return self._gemv_raw(x, ws, residual, epilogue, self.splits, bias)
 
     def dense(self) -> torch.Tensor:
