@@ -124,7 +124,17 @@ torch::Tensor rms_norm_f32out(torch::Tensor x, torch::Tensor w, double eps) {
 
 // ------------------------------------------------------------- layer_norm
 
-// one workgroup (256 threads) per row, two-pass mean/variance in registers;
+// one workgroup per row (T = 1024 threads for rows <= 4, else 256), corrected
+// two-pass mean/variance: the first pass sums x for the mean, the second sums
+// c = x - mean and c^2. The one-pass E[x^2] - mean^2 it replaces cancels in
+// fp32 when |mean| >> std (mean 32, std 0.05: inv off by 1-2 %); the squares
+// of the centred values do not. An fp32 mean is itself only good to
+// 2^-24 |mean|, which is not small next to an element close to the mean of an
+// offset row, so d = sum(c) / dim (what the rounded mean missed) is taken off
+// again: var = sum(c^2) / dim - d^2 and y = (c - d) * inv * w + b. c is exact
+// for x within a factor 2 of the mean, so (c - d) must stay two subtractions:
+// reassociating it into x - (mean + d) would round the correction away, hence
+// the pragma. The row is re-read from L1/L2 in each pass.
 // BLOOM/Falcon blocks use LayerNorm with bias where Llama uses RMSNorm
 // (reference models/bloom/block.py wraps HF BloomBlock whose norms run in
 // torch; here the norm is one fused kernel feeding the gemv in f32).
@@ -136,47 +146,68 @@ __global__ void layer_norm_kernel(
     void* __restrict__ y,                  // [rows, dim] bf16 or f32
     int dim,
     float eps) {
+#pragma clang fp reassociate(off)
   const int row = blockIdx.x;
   const int tid = threadIdx.x;
   const unsigned short* xr = x + (size_t)row * dim;
-
-  float sum = 0.f, sumsq = 0.f;
+  __shared__ float red_s[T / WAVE];
+  __shared__ float red_c[T / WAVE];
+  __shared__ float red_q[T / WAVE];
   const int chunk = T * 8;
+
+  float sum = 0.f;
+  for (int base = 0; base < dim; base += chunk) {
+    const int idx = base + tid * 8;
+    if (idx + 8 <= dim) {
+      const short8 v = *reinterpret_cast<const short8*>(xr + idx);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sum += bf16_to_f32((unsigned short)v[j]);
+    } else {
+      for (int j = idx; j < dim; ++j) sum += bf16_to_f32(xr[j]);
+    }
+  }
+  sum = wave_reduce_sum(sum);
+  if ((tid & (WAVE - 1)) == 0) red_s[tid / WAVE] = sum;
+  __syncthreads();
+  float tot_s = 0.f;
+#pragma unroll
+  for (int i = 0; i < T / WAVE; ++i) tot_s += red_s[i];
+  const float mean = tot_s / dim;
+
+  float sumc = 0.f, sumsq = 0.f;
   for (int base = 0; base < dim; base += chunk) {
     const int idx = base + tid * 8;
     if (idx + 8 <= dim) {
       const short8 v = *reinterpret_cast<const short8*>(xr + idx);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float f = bf16_to_f32((unsigned short)v[j]);
-        sum += f;
-        sumsq = fmaf(f, f, sumsq);
+        const float c = bf16_to_f32((unsigned short)v[j]) - mean;
+        sumc += c;
+        sumsq = fmaf(c, c, sumsq);
       }
     } else {
       for (int j = idx; j < dim; ++j) {
-        const float f = bf16_to_f32(xr[j]);
-        sum += f;
-        sumsq = fmaf(f, f, sumsq);
+        const float c = bf16_to_f32(xr[j]) - mean;
+        sumc += c;
+        sumsq = fmaf(c, c, sumsq);
       }
     }
   }
-  __shared__ float red_s[T / WAVE];
-  __shared__ float red_q[T / WAVE];
-  sum = wave_reduce_sum(sum);
+  sumc = wave_reduce_sum(sumc);
   sumsq = wave_reduce_sum(sumsq);
   if ((tid & (WAVE - 1)) == 0) {
-    red_s[tid / WAVE] = sum;
+    red_c[tid / WAVE] = sumc;
     red_q[tid / WAVE] = sumsq;
   }
   __syncthreads();
-  float tot_s = 0.f, tot_q = 0.f;
+  float tot_c = 0.f, tot_q = 0.f;
 #pragma unroll
   for (int i = 0; i < T / WAVE; ++i) {
-    tot_s += red_s[i];
+    tot_c += red_c[i];
     tot_q += red_q[i];
   }
-  const float mean = tot_s / dim;
-  const float var = tot_q / dim - mean * mean;
+  const float d = tot_c / dim;
+  const float var = tot_q / dim - d * d;
   const float inv = rsqrtf(var + eps);
 
   for (int base = 0; base < dim; base += chunk) {
@@ -187,8 +218,8 @@ __global__ void layer_norm_kernel(
       const short8 bv = *reinterpret_cast<const short8*>(bias + idx);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float f = (bf16_to_f32((unsigned short)v[j]) - mean) * inv *
-                            bf16_to_f32((unsigned short)wv[j]) +
+        const float c = bf16_to_f32((unsigned short)v[j]) - mean;
+        const float f = (c - d) * inv * bf16_to_f32((unsigned short)wv[j]) +
                         bf16_to_f32((unsigned short)bv[j]);
         if (OUT_F32)
           reinterpret_cast<float*>(y)[(size_t)row * dim + idx + j] = f;
@@ -197,7 +228,8 @@ __global__ void layer_norm_kernel(
       }
     } else {
       for (int j = idx; j < dim; ++j) {
-        const float f = (bf16_to_f32(xr[j]) - mean) * inv * bf16_to_f32(w[j]) + bf16_to_f32(bias[j]);
+        const float c = bf16_to_f32(xr[j]) - mean;
+        const float f = (c - d) * inv * bf16_to_f32(w[j]) + bf16_to_f32(bias[j]);
         if (OUT_F32)
           reinterpret_cast<float*>(y)[(size_t)row * dim + j] = f;
         else

@@ -591,6 +591,7 @@ torch::Tensor gemv_bf16_moe(
   const int rows = sel.size(0);
   TORCH_CHECK(x.size(1) == in_dim && rows == x.size(0) * k_per_tok);
   TORCH_CHECK(rows <= 16, "moe gemv supports batch*k <= 16");
+  TORCH_CHECK(epilogue >= 0, "gemv_bf16_moe has no raw-partials mode");
 
   const long out_waves = (out_dim + GEMV_OUT_PER_WAVE - 1) / GEMV_OUT_PER_WAVE;
   long splits = splits_override > 0 ? splits_override : (768 + out_waves * rows - 1) / (out_waves * rows);
@@ -634,6 +635,7 @@ torch::Tensor gemv_nf4_moe(
   const int rows = sel.size(0);
   TORCH_CHECK(x.size(1) == in_dim && rows == x.size(0) * k_per_tok);
   TORCH_CHECK(rows <= 16, "moe gemv supports batch*k <= 16");
+  TORCH_CHECK(epilogue >= 0, "gemv_nf4_moe has no raw-partials mode");
 
   const long out_waves = (out_dim + NF4_OUT_PER_WAVE - 1) / NF4_OUT_PER_WAVE;
   long splits = splits_override > 0 ? splits_override : (1536 + out_waves * rows - 1) / (out_waves * rows);
