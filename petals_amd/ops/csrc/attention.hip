@@ -10,7 +10,9 @@
 // splits. Measured (scripts/decode_mfma.hip, llama-2-70b shape): 1039 GB/s at
 // kv=4k -> 3509 GB/s at kv=131k, 2.2-2.4x the original VALU kernel (16-lane-
 // group dot products, online softmax in registers; removed, see
-// docs/KERNELS.md) at every length.
+// docs/KERNELS.md) at every length. Those figures predate the batched loads
+// ("Loads" below), which took benchmarks/benchmark_kv_fp8.py (rotating
+// caches) from 577 to 751 GB/s at 4k and from 3335 to 4376 GB/s at 131k.
 //
 // kv_len comes from a DEVICE pointer so the whole decode step can be captured
 // in a hipGraph with a moving position.
@@ -43,8 +45,42 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 // instead of bf16. Only the two global reads differ: the K B-fragment is 8
 // bytes per lane and V rows arrive as 8-byte chunks, both converted (exactly)
 // to the bf16x8 the bf16 instantiation loads. Everything downstream is shared.
+//
+// Loads: q (and the ALiBi slopes) arrive in one batch in the prologue, and a
+// tile's V chunks and K fragments are loaded into registers in one batch
+// before anything consumes them (DecodeTile), so a tile costs one memory
+// round trip instead of one per load group. (Issuing the wave's next tile
+// under the softmax and PV of the current one was measured and did not win,
+// see docs/KERNELS.md.)
+template <int HD, bool FP8>
+struct DecodeTile {
+  static constexpr int VN = DKVT * (HD / 8) / WAVE;  // V chunks of 8 elements per lane
+  using raw_t = typename std::conditional<FP8, uint2, bf16x8>::type;
+  raw_t v[VN];
+  raw_t k[DKVT / 16][HD / 32];
+  static __device__ __forceinline__ bf16x8 to_bf16(raw_t w) {
+    if constexpr (FP8)
+      return e4m3x8_to_bf16x8(w);
+    else
+      return w;
+  }
+};
+
+// s_waitcnt lgkmcnt(0) alone (gfx9 encoding: vmcnt and expcnt at their
+// maxima), so global loads in flight are not waited for
+#define WAIT_LGKM0 0xC07F
+
+// Waves per SIMD the register allocation must leave room for: LDS admits 3
+// workgroups per CU at HD 128 (168 registers per lane) and the split policy
+// uses them at long caches; HD 64 keeps the 4 it had. The one form that does
+// not fit 168 without scratch, bf16 HD 128 with two head groups, gets 2.
+constexpr int decode_waves_per_simd(int hd, int gq, bool fp8) {
+  return hd == 128 ? (!fp8 && gq > 16 ? 2 : 3) : 4;
+}
+
 template <int HD, int GQ, bool FP8 = false>
-__global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
+__global__ __launch_bounds__(DWAVES * 64) __attribute__((amdgpu_waves_per_eu(decode_waves_per_simd(HD, GQ, FP8))))
+void mfma_decode_kernel(
     const float* __restrict__ q,            // [B, KV, GQ, HD]
     const typename std::conditional<FP8, unsigned char, unsigned short>::type* __restrict__ k_cache,  // [B, KV, lmax, HD]
     const typename std::conditional<FP8, unsigned char, unsigned short>::type* __restrict__ v_cache,
@@ -68,7 +104,7 @@ __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
   const int j_end = min(j_begin + rows_per_split, kv_len);
 
   const int tid = threadIdx.x;
-  const int wave = tid / WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);  // scalar: tile indices and loop control stay in SGPRs
   const int lane = tid & (WAVE - 1);
   const int col = lane & 15;
   const int hi = lane >> 4;
@@ -94,26 +130,35 @@ __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
     if (a > 0) __syncthreads();  // wave0's combine reads of vt_raw are done
 
     // ---- q tile: A-fragment rows = q heads of this group (zero-padded), pre-scaled
-    bf16x8 q_frag[KCH];
+    // One batch: every load of the fragment (and of the slopes) is issued
+    // before the first is consumed. Padding rows load a clamped head and are
+    // zeroed afterwards, so no load sits behind a branch; none of the
+    // addresses depends on kv_len, whose load overlaps them.
+    const unsigned short q_mask = g0 + col < GQ ? 0xFFFFu : 0u;  // a mask, not a branch per element
+    const float* q_src = q + q_base + (size_t)min(g0 + col, GQ - 1) * HD + hi * 8;
+    f32x4 q_raw[KCH][2];
 #pragma unroll
     for (int kc = 0; kc < KCH; ++kc) {
-      if (g0 + col < GQ) {
-        const float* src = q + q_base + (size_t)(g0 + col) * HD + kc * 32 + hi * 8;
-        short v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (short)f32_to_bf16(src[e] * scale);
-        q_frag[kc] = bf16x8{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
-      } else {
-        q_frag[kc] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
+      q_raw[kc][0] = *reinterpret_cast<const f32x4*>(q_src + kc * 32);
+      q_raw[kc][1] = *reinterpret_cast<const f32x4*>(q_src + kc * 32 + 4);
     }
 
     // per-lane-row ALiBi slopes (rows = heads g0 + hi*4 + r)
-    float sl[4];
+    float sl[4] = {0.f, 0.f, 0.f, 0.f};
+    if (alibi) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int g = g0 + hi * 4 + r;
-      sl[r] = (alibi && g < GQ) ? alibi[kvh * GQ + g] : 0.f;
+      for (int r = 0; r < 4; ++r) sl[r] = alibi[kvh * GQ + min(g0 + hi * 4 + r, GQ - 1)];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (g0 + hi * 4 + r >= GQ) sl[r] = 0.f;
+    }
+
+    bf16x8 q_frag[KCH];
+#pragma unroll
+    for (int kc = 0; kc < KCH; ++kc) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        q_frag[kc][e] = (short)(f32_to_bf16(q_raw[kc][e >> 2][e & 3] * scale) & q_mask);
     }
 
     f32x4 acc_o[HD / 16];
@@ -126,46 +171,73 @@ __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
       l_row[r] = 0.f;
     }
 
+    // A tile's K B-fragments and V chunks (VN per lane) go to registers in
+    // one batch of unconditional loads, K first because the QK MFMAs consume
+    // it first: rows past j_end are clamped to j_end - 1 (every address stays
+    // inside [j_begin, j_end)); V rows past j_end become zeros when they are
+    // written to LDS. Offsets inside one (batch, head) are computed in 32
+    // bits (the host checks lmax * HD), which keeps the address arithmetic
+    // of the 16 loads short.
+    DecodeTile<HD, FP8> tile;
+    const auto load_tile = [&](int j0) {
+#pragma unroll
+      for (int nb = 0; nb < DKVT / 16; ++nb) {
+        const auto* krow = kb + ((unsigned)min(j0 + nb * 16 + col, j_end - 1) * HD + hi * 8);
+#pragma unroll
+        for (int kc = 0; kc < KCH; ++kc)
+          tile.k[nb][kc] = *reinterpret_cast<const typename DecodeTile<HD, FP8>::raw_t*>(krow + kc * 32);
+      }
+#pragma unroll
+      for (int i = 0; i < tile.VN; ++i) {
+        const int idx = lane + i * WAVE;
+        const int row = idx / (HD / 8);
+        const int c8 = (idx - row * (HD / 8)) * 8;
+        tile.v[i] = *reinterpret_cast<const typename DecodeTile<HD, FP8>::raw_t*>(
+            vb + ((unsigned)min(j0 + row, j_end - 1) * HD + c8));
+      }
+      // nothing that waits for a load may be scheduled among the loads
+      __builtin_amdgcn_sched_barrier(0);
+    };
+
     // wave w handles tiles j_begin + (t*DWAVES + w)*DKVT
     for (int j0 = j_begin + wave * DKVT; j0 < j_end; j0 += DWAVES * DKVT) {
       const int tile_n = min(DKVT, j_end - j0);
       const bool full = tile_n == DKVT;
+      load_tile(j0);
 
-      // ---- stage V^T (this wave only: no block barrier; the waitcnt orders
-      // this wave's LDS writes before its reads)
-      for (int idx = lane; idx < DKVT * (HD / 8); idx += WAVE) {
-        const int row = idx / (HD / 8);
-        const int c8 = (idx - row * (HD / 8)) * 8;
-        bf16x8 vv8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (j0 + row < j_end) {
-          if constexpr (FP8)
-            vv8 = e4m3x8_to_bf16x8(*reinterpret_cast<const uint2*>(vb + (size_t)(j0 + row) * HD + c8));
-          else
-            vv8 = *reinterpret_cast<const bf16x8*>(vb + (size_t)(j0 + row) * HD + c8);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          *reinterpret_cast<unsigned short*>(&vt_raw[wave][DVT_BYTE(c8 + e, row * 2)]) = (unsigned short)vv8[e];
-      }
-      __builtin_amdgcn_s_waitcnt(0);
-
-      // ---- S = Q K^T, K direct from global: B[k = kdim][n = key]
+      // ---- S = Q K^T, K from the tile registers: B[k = kdim][n = key]
       f32x4 s_acc[DKVT / 16];
 #pragma unroll
       for (int nb = 0; nb < DKVT / 16; ++nb) {
         s_acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int key = j0 + nb * 16 + col;
-        const auto* krow = kb + (size_t)min(key, j_end - 1) * HD + hi * 8;
 #pragma unroll
-        for (int kc = 0; kc < KCH; ++kc) {
-          bf16x8 kt;
-          if constexpr (FP8)
-            kt = e4m3x8_to_bf16x8(*reinterpret_cast<const uint2*>(krow + kc * 32));
-          else
-            kt = *reinterpret_cast<const bf16x8*>(krow + kc * 32);
-          s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q_frag[kc], kt, s_acc[nb], 0, 0, 0);
-        }
+        for (int kc = 0; kc < KCH; ++kc)
+          s_acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q_frag[kc], tile.to_bf16(tile.k[nb][kc]), s_acc[nb], 0, 0, 0);
       }
+      __builtin_amdgcn_sched_barrier(0);  // K registers are free before V is unpacked
+
+      // ---- stage V^T (this wave only: no block barrier; a wave's LDS
+      // accesses complete in order, the lgkmcnt wait orders them for the
+      // compiler).
+      // The 8 * VN swizzled addresses do not depend on the tile. The opaque
+      // copy of the lane keeps them from being hoisted out of the tile loop
+      // (64 VGPRs at HD 128), the fence from being computed all up front:
+      // they are recomputed per chunk, as the rolled loop did.
+      int st_lane = lane;
+      asm volatile("" : "+v"(st_lane));
+#pragma unroll
+      for (int i = 0; i < tile.VN; ++i) {
+        const int idx = st_lane + i * WAVE;
+        const int row = idx / (HD / 8);
+        const int c8 = (idx - row * (HD / 8)) * 8;
+        bf16x8 vv8 = tile.to_bf16(tile.v[i]);
+        if (j0 + row >= j_end) vv8 = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          *reinterpret_cast<unsigned short*>(&vt_raw[wave][DVT_BYTE(c8 + e, row * 2)]) = (unsigned short)vv8[e];
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
 
       // ---- online softmax over this tile (rows = heads g0 + hi*4+r)
       float p[DKVT / 16][4];
@@ -203,7 +275,7 @@ __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
 #pragma unroll
         for (int nb = 0; nb < DKVT / 16; ++nb)
           p_lds[wave][hi * 4 + r][nb * 16 + col] = f32_to_bf16(p[nb][r]);
-      __builtin_amdgcn_s_waitcnt(0);
+      __builtin_amdgcn_s_waitcnt(WAIT_LGKM0);
 
       const bf16x8 p_frag = *reinterpret_cast<const bf16x8*>(&p_lds[wave][col][hi * 8]);
 
@@ -268,25 +340,48 @@ __global__ __launch_bounds__(DWAVES * 64) void mfma_decode_kernel(
   }
 }
 
+// Merges the splits of one (batch, kv head, q head). The m / l pairs and the
+// O values of COMBINE_BATCH splits are loaded together and then accumulated
+// one split after the other, in split order: the sums are those of a plain
+// loop over the splits (reassociation is switched off for them), but a
+// 64-split cache pays 8 load round trips instead of 64.
+#define COMBINE_BATCH 8
+
 __global__ void attn_decode_combine_kernel(
     const float* __restrict__ part_o,   // [B*KV, splits, GQ, HD]
     const float* __restrict__ part_ml,  // [B*KV, splits, GQ, 2]
     float* __restrict__ out,            // [B, KV*GQ*HD]
     int n_splits, int gq, int hd) {
+#pragma clang fp reassociate(off)
   const int bkv = blockIdx.x;
   const int g = blockIdx.y;
+  // row of split s in both workspaces; loads past the last split repeat it
+  const auto row = [&](int s) { return ((size_t)bkv * n_splits + min(s, n_splits - 1)) * gq + g; };
   float m_star = NEG_SENTINEL;
-  for (int s = 0; s < n_splits; ++s)
-    m_star = fmaxf(m_star, part_ml[(((size_t)bkv * n_splits + s) * gq + g) * 2]);
+  for (int s0 = 0; s0 < n_splits; s0 += COMBINE_BATCH) {
+    float ms[COMBINE_BATCH];
+#pragma unroll
+    for (int i = 0; i < COMBINE_BATCH; ++i) ms[i] = part_ml[row(s0 + i) * 2];
+#pragma unroll
+    for (int i = 0; i < COMBINE_BATCH; ++i) m_star = fmaxf(m_star, ms[i]);
+  }
   for (int d = threadIdx.x; d < hd; d += blockDim.x) {
     float osum = 0.f, lsum = 0.f;
-    for (int s = 0; s < n_splits; ++s) {
-      const float ms = part_ml[(((size_t)bkv * n_splits + s) * gq + g) * 2];
-      const float ls = part_ml[(((size_t)bkv * n_splits + s) * gq + g) * 2 + 1];
-      if (ms <= NEG_THRESHOLD) continue;
-      const float w = __expf(ms - m_star);
-      osum += w * part_o[(((size_t)bkv * n_splits + s) * gq + g) * hd + d];
-      lsum += w * ls;
+    for (int s0 = 0; s0 < n_splits; s0 += COMBINE_BATCH) {
+      float ms[COMBINE_BATCH], ls[COMBINE_BATCH], po[COMBINE_BATCH];
+#pragma unroll
+      for (int i = 0; i < COMBINE_BATCH; ++i) {
+        ms[i] = part_ml[row(s0 + i) * 2];
+        ls[i] = part_ml[row(s0 + i) * 2 + 1];
+        po[i] = part_o[row(s0 + i) * hd + d];
+      }
+#pragma unroll
+      for (int i = 0; i < COMBINE_BATCH; ++i) {
+        if (s0 + i >= n_splits || ms[i] <= NEG_THRESHOLD) continue;
+        const float w = __expf(ms[i] - m_star);
+        osum += w * po[i];
+        lsum += w * ls[i];
+      }
     }
     out[(size_t)bkv * gq * hd + (size_t)g * hd + d] = osum / fmaxf(lsum, 1e-20f);
   }
@@ -317,6 +412,7 @@ torch::Tensor attn_decode_fused(
   const int b = q.size(0);
   TORCH_CHECK(b <= k_cache.size(0), "more q rows than cache rows");
   const int kv_heads = k_cache.size(1), lmax = k_cache.size(2), hd = k_cache.size(3);
+  TORCH_CHECK((int64_t)lmax * hd < (int64_t(1) << 32), "one (batch, head) of the cache must stay below 2^32 elements");
   const int GQi = (int)gq;
   int n_splits = (int)n_splits_i;
   if (n_splits <= 0) {
