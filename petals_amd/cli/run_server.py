@@ -69,6 +69,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--kv_cache_dtype", type=str, default="bf16", choices=["bf16", "fp8"],
                         help="KV-cache element type: bf16, or fp8 (OCP E4M3, no scales; fused Llama / "
                              "Mixtral blocks on one GPU) for half the cache bytes per token")
+    parser.add_argument("--multi_decode", type=str, default="off", choices=["off", "on"],
+                        help="steps of 2..8 new tokens against the KV cache (speculative verify) on Llama "
+                             "blocks: the prefill path (off) or the multi-token decode kernel chain (on)")
     parser.add_argument("--attn_cache_tokens", type=int, default=16384)
     parser.add_argument("--max_batch_size", type=int, default=8)
     parser.add_argument("--max_chunk_size_bytes", type=int, default=256 * 1024 * 1024,
@@ -159,6 +162,11 @@ def main(argv=None):
 
         set_prefill_gemm_mode(args.prefill_gemm)
 
+    if args.multi_decode != "off":
+        from petals_amd.ops.fused_decode import set_multi_decode_mode
+
+        set_multi_decode_mode(args.multi_decode)
+
     if args.tensor_parallel_ranks > 1:
         # launched under torchrun, one process per GPU: rank 0 is the swarm
         # Server; ranks 1.. execute their block shards in lockstep
@@ -234,6 +242,7 @@ def main(argv=None):
         tensor_parallel_ranks=args.tensor_parallel_ranks,
         prefill_gemm=args.prefill_gemm,
         kv_cache_dtype=args.kv_cache_dtype,
+        multi_decode=args.multi_decode,
     )
     server.start()
     print(f"petals_amd server listening on {server.listen_addr} peer_id={server.peer_id}", flush=True)

@@ -21,6 +21,16 @@ torch::Tensor qkv_rope_reduce(
     torch::Tensor partials, c10::optional<torch::Tensor> cos_t, c10::optional<torch::Tensor> sin_t,
     torch::Tensor pos, torch::Tensor k_cache, torch::Tensor v_cache,
     int64_t qh, int64_t kh, bool rope, c10::optional<torch::Tensor> bias);
+torch::Tensor qkv_rope_reduce_multi(
+    torch::Tensor partials, torch::Tensor cos_t, torch::Tensor sin_t, torch::Tensor pos,
+    torch::Tensor k_cache, torch::Tensor v_cache, int64_t qh, int64_t kh, int64_t tokens);
+void rope_cache_write_multi(
+    torch::Tensor qkv, torch::Tensor cos_t, torch::Tensor sin_t, torch::Tensor pos,
+    torch::Tensor k_cache, torch::Tensor v_cache, int64_t qh, int64_t kh, int64_t tokens);
+torch::Tensor attn_decode_multi(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor pos,
+    int64_t tokens, int64_t gq, int64_t n_splits, torch::Tensor part_o, torch::Tensor part_ml,
+    double scale);
 torch::Tensor gemv_bf16(
     torch::Tensor wt, torch::Tensor x, torch::Tensor workspace,
     c10::optional<torch::Tensor> residual, int64_t epilogue, int64_t splits_override,
@@ -99,6 +109,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"), py::arg("gq"),
         py::arg("n_splits"), py::arg("part_o"), py::arg("part_ml"), py::arg("scale"),
         py::arg("alibi_slopes") = py::none());
+  m.def("attn_decode_multi", &attn_decode_multi,
+        "causal split-KV decode attention for a step of 1..8 new tokens per sequence "
+        "(q rows b*T + t; the new K/V rows are in the cache at pos .. pos+T-1)",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("pos"), py::arg("tokens"),
+        py::arg("gq"), py::arg("n_splits"), py::arg("part_o"), py::arg("part_ml"), py::arg("scale"));
+  m.def("qkv_rope_reduce_multi", &qkv_rope_reduce_multi,
+        "qkv_rope_reduce (rope form) for a step of T tokens per sequence: row r -> cache batch "
+        "r / T, position pos + r % T",
+        py::arg("partials"), py::arg("cos_t"), py::arg("sin_t"), py::arg("pos"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("qh"), py::arg("kh"), py::arg("tokens"));
+  m.def("rope_cache_write_multi", &rope_cache_write_multi,
+        "rope_cache_write for a step of T tokens per sequence",
+        py::arg("qkv"), py::arg("cos_t"), py::arg("sin_t"), py::arg("pos"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("qh"), py::arg("kh"), py::arg("tokens"));
   m.def("attn_prefill_fused", &attn_prefill_fused, "MFMA flash prefill attention (bf16, causal, GQA)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kv_len"), py::arg("kv_offset"),
         py::arg("scale"), py::arg("causal"), py::arg("alibi_slopes") = py::none());

@@ -678,6 +678,199 @@ void rope_cache_write(
   HIP_CHECK_LAST();
 }
 
+// ------------------------- multi-token decode step: T rows per sequence
+// The two rope writers above for a step of T = 1..8 new tokens per sequence
+// (attn_multi.hip): row r of the [.., B*T, row_elems] input belongs to cache
+// batch r / T and to position *pos + r % T, whose rope row it uses. Separate
+// kernels, so the single-token ones keep their compiled form; the reduce sums
+// the splits in the same order (16 groups, then the groups).
+
+template <typename CT>
+__global__ void rope_cache_write_multi_kernel(
+    float* __restrict__ qkv,  // [rows, row_elems]
+    const float* __restrict__ cos_t,
+    const float* __restrict__ sin_t,
+    const int* __restrict__ pos_ptr,
+    CT* __restrict__ k_cache,  // [bcap, kh, lmax, hd]
+    CT* __restrict__ v_cache,
+    int rows, int tokens, int qh, int kh, int lmax, int hd) {
+  const int half = hd / 2;
+  const int p0 = *pos_ptr;
+  const int row_elems = qh * hd + 2 * kh * hd;
+  const long rot_total = (long)rows * (qh + kh) * half;
+  const long v_total = (long)rows * kh * hd;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < rot_total + v_total;
+       idx += (long)gridDim.x * blockDim.x) {
+    if (idx < rot_total) {
+      long t = idx;
+      const int d = t % half; t /= half;
+      const int h = t % (qh + kh); t /= (qh + kh);
+      const int r = t;
+      const int bi = r / tokens, p = p0 + (r - bi * tokens);
+      const float c = cos_t[(size_t)p * hd + d], s = sin_t[(size_t)p * hd + d];
+      float* base = qkv + (size_t)r * row_elems + h * hd;
+      const float x1 = base[d], x2 = base[d + half];
+      if (h < qh) {
+        base[d] = x1 * c - x2 * s;
+        base[d + half] = x2 * c + x1 * s;
+      } else {
+        CT* krow = k_cache + (((size_t)bi * kh + (h - qh)) * lmax + p) * hd;
+        krow[d] = f32_to_kv<CT>(x1 * c - x2 * s);
+        krow[d + half] = f32_to_kv<CT>(x2 * c + x1 * s);
+      }
+    } else {
+      long t = idx - rot_total;
+      const int d = t % hd; t /= hd;
+      const int kh_i = t % kh; t /= kh;
+      const int r = t;
+      const int bi = r / tokens, p = p0 + (r - bi * tokens);
+      const float v = qkv[(size_t)r * row_elems + qh * hd + kh * hd + kh_i * hd + d];
+      v_cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + d] = f32_to_kv<CT>(v);
+    }
+  }
+}
+
+template <typename CT>
+__global__ __launch_bounds__(64 * QKV_RED_GROUPS) void qkv_rope_reduce_multi_kernel(
+    const float* __restrict__ partials,  // [splits, rows, row_elems]
+    const float* __restrict__ cos_t,     // [max_pos, hd]
+    const float* __restrict__ sin_t,
+    const int* __restrict__ pos_ptr,
+    float* __restrict__ q_out,             // [rows, qh*hd] f32 (rotated)
+    CT* __restrict__ k_cache,              // [bcap, kh, lmax, hd] bf16 or e4m3
+    CT* __restrict__ v_cache,
+    int n_splits, int rows, int tokens, int qh, int kh, int lmax, int hd) {
+  constexpr int G = QKV_RED_GROUPS;
+  __shared__ float acc_a[G][64];
+  __shared__ float acc_b[G][64];
+  const int half = hd >> 1;
+  const int row_elems = qh * hd + 2 * kh * hd;
+  const int total = rows * row_elems;
+  const int ol = threadIdx.x & 63;
+  const int sg = threadIdx.x >> 6;
+  const int idx = blockIdx.x * 64 + ol;
+  const bool live = idx < total;
+  const int r = live ? idx / row_elems : 0;
+  const int o = live ? idx - r * row_elems : 0;
+  const size_t stride = (size_t)rows * row_elems;
+  const size_t row = (size_t)r * row_elems;
+
+  const bool in_q = o < qh * hd;
+  const bool in_k = !in_q && o < qh * hd + kh * hd;
+  const int d = in_q ? (o % hd) : (in_k ? ((o - qh * hd) % hd) : 0);
+  const bool rotate = in_q || in_k;
+  const int partner = rotate ? (d < half ? o + half : o - half) : o;
+
+  float a = 0.f, p2 = 0.f;
+  if (live) {
+    for (int s = sg; s < n_splits; s += G) a += partials[(size_t)s * stride + row + o];
+    if (rotate)
+      for (int s = sg; s < n_splits; s += G) p2 += partials[(size_t)s * stride + row + partner];
+  }
+  acc_a[sg][ol] = a;
+  acc_b[sg][ol] = p2;
+  __syncthreads();
+  if (sg != 0 || !live) return;
+  float sum = 0.f, psum = 0.f;
+#pragma unroll
+  for (int k = 0; k < G; ++k) {
+    sum += acc_a[k][ol];
+    psum += acc_b[k][ol];
+  }
+
+  const int bi = r / tokens;
+  const int p = *pos_ptr + (r - bi * tokens);
+  float val = sum;
+  if (rotate) {
+    const float c = cos_t[(size_t)p * hd + (d < half ? d : d - half)];
+    const float s = sin_t[(size_t)p * hd + (d < half ? d : d - half)];
+    val = (d < half) ? (sum * c - psum * s) : (sum * c + psum * s);
+  }
+  if (in_q) {
+    q_out[(size_t)r * qh * hd + o] = val;
+  } else if (in_k) {
+    const int kh_i = (o - qh * hd) / hd;
+    k_cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + d] = f32_to_kv<CT>(val);
+  } else {
+    const int t = o - qh * hd - kh * hd;
+    const int kh_i = t / hd;
+    const int dv = t - kh_i * hd;
+    v_cache[(((size_t)bi * kh + kh_i) * lmax + p) * hd + dv] = f32_to_kv<CT>(val);
+  }
+}
+
+// rows = B * tokens; the rope tables must cover *pos + tokens rows and the
+// caches *pos + tokens positions (the position is device-resident, so the
+// caller guarantees both)
+static bool check_multi_step(const torch::Tensor& k_cache, const torch::Tensor& v_cache,
+                             const torch::Tensor& cos_t, const torch::Tensor& sin_t,
+                             const torch::Tensor& pos, int64_t rows, int64_t tokens) {
+  TORCH_CHECK(1 <= tokens && tokens <= 8, "a multi-token decode step takes 1..8 tokens per sequence, got ", tokens);
+  TORCH_CHECK(rows >= tokens && rows % tokens == 0, "rows must be B * tokens");
+  TORCH_CHECK(tokens <= k_cache.size(2), "the cache is shorter than the step");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kInt && pos.numel() == 1, "pos must be a device int32 scalar");
+  TORCH_CHECK(cos_t.is_cuda() && cos_t.dtype() == torch::kFloat32 && cos_t.is_contiguous() && cos_t.dim() == 2 &&
+                  cos_t.size(1) == k_cache.size(3) && sin_t.is_cuda() && sin_t.dtype() == torch::kFloat32 &&
+                  sin_t.is_contiguous() && sin_t.sizes() == cos_t.sizes(),
+              "rope tables must be contiguous f32 [positions, head_dim]");
+  return check_kv_caches(k_cache, v_cache, rows / tokens);
+}
+
+torch::Tensor qkv_rope_reduce_multi(
+    torch::Tensor partials,  // [splits, B*T, row_elems] f32 (RAW gemv output), row b*T + t
+    torch::Tensor cos_t, torch::Tensor sin_t,
+    torch::Tensor pos,       // device int32 [1]: prefix length before the step
+    torch::Tensor k_cache,   // [bcap, kh, lmax, hd] bf16 or float8_e4m3fn
+    torch::Tensor v_cache,
+    int64_t qh, int64_t kh, int64_t tokens) {
+  TORCH_CHECK(partials.is_cuda() && partials.dtype() == torch::kFloat32 && partials.dim() == 3 &&
+              partials.is_contiguous());
+  const int n_splits = partials.size(0);
+  const int rows = partials.size(1);
+  const bool fp8 = check_multi_step(k_cache, v_cache, cos_t, sin_t, pos, rows, tokens);
+  const int lmax = k_cache.size(2), hd = k_cache.size(3);
+  TORCH_CHECK(k_cache.size(1) == kh);
+  TORCH_CHECK(partials.size(2) == qh * hd + 2 * kh * hd, "qkv width mismatch");
+  auto q_out = torch::empty({(int64_t)rows, qh * hd}, partials.options());
+  const int total = rows * (int)partials.size(2);
+  const int blocks = (total + 63) / 64;
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define LAUNCH_QRRM(CT)                                                          \
+  qkv_rope_reduce_multi_kernel<CT><<<blocks, 64 * QKV_RED_GROUPS, 0, stream>>>(  \
+      partials.data_ptr<float>(), cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), \
+      pos.data_ptr<int>(), q_out.data_ptr<float>(),                              \
+      reinterpret_cast<CT*>(k_cache.data_ptr()),                                 \
+      reinterpret_cast<CT*>(v_cache.data_ptr()),                                 \
+      n_splits, rows, (int)tokens, (int)qh, (int)kh, lmax, hd)
+  if (fp8) LAUNCH_QRRM(unsigned char); else LAUNCH_QRRM(unsigned short);
+#undef LAUNCH_QRRM
+  HIP_CHECK_LAST();
+  return q_out;
+}
+
+void rope_cache_write_multi(
+    torch::Tensor qkv, torch::Tensor cos_t, torch::Tensor sin_t, torch::Tensor pos,
+    torch::Tensor k_cache, torch::Tensor v_cache, int64_t qh, int64_t kh, int64_t tokens) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.dtype() == torch::kFloat32 && qkv.dim() == 2 && qkv.is_contiguous());
+  const int rows = qkv.size(0);
+  const bool fp8 = check_multi_step(k_cache, v_cache, cos_t, sin_t, pos, rows, tokens);
+  const int hd = k_cache.size(3), lmax = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(1) == kh && qkv.size(1) == (qh + 2 * kh) * hd, "qkv width mismatch");
+  const long total = (long)rows * (qh + kh) * (hd / 2) + (long)rows * kh * hd;
+  const long blocks = std::min((total + 255) / 256 + 1, (long)1024);
+  auto stream = at::cuda::getCurrentCUDAStream();
+#define LAUNCH_RCWM(CT)                                                         \
+  rope_cache_write_multi_kernel<CT><<<blocks, 256, 0, stream>>>(                \
+      qkv.data_ptr<float>(), cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),  \
+      pos.data_ptr<int>(),                                                      \
+      reinterpret_cast<CT*>(k_cache.data_ptr()),                                \
+      reinterpret_cast<CT*>(v_cache.data_ptr()),                                \
+      rows, (int)tokens, (int)qh, (int)kh, lmax, hd)
+  if (fp8) LAUNCH_RCWM(unsigned char); else LAUNCH_RCWM(unsigned short);
+#undef LAUNCH_RCWM
+  HIP_CHECK_LAST();
+}
+
 // ------------------------------------------- prefill store into an fp8 cache
 // new_kv [B, KV, S, hd] bf16 -> cache[:B, :, prefix:prefix+S] as OCP E4M3 with
 // the decode writers' rounding (clamp to +-448, round to nearest even, NaN

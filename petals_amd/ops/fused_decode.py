@@ -110,6 +110,32 @@ def set_prefill_gemm_mode(mode: str) -> None:
     os.environ["PETALS_AMD_PREFILL_GEMM"] = mode
 
 
+_MULTI_DECODE_MODES = ("off", "on")
+MULTI_DECODE_MAX_ROWS = 8  # B * T rows the GEMVs run natively
+MULTI_DECODE_MAX_GQ = 16  # one 16-row MFMA group holds the q heads of a kv head
+
+
+def multi_decode_mode() -> str:
+    """How a Llama block runs a step of 2..8 new tokens against its KV cache (a
+    speculative-decoding verify step), read at call time from
+    PETALS_AMD_MULTI_DECODE: `off` (default) is the prefill path
+    (LlamaFastPath.forward); `on` is the decode kernel chain on B*T rows with
+    the causal multi-token attention kernel (LlamaFastPath.decode_multi)."""
+    mode = os.environ.get("PETALS_AMD_MULTI_DECODE", "off")
+    if mode not in _MULTI_DECODE_MODES:
+        raise ValueError(
+            f"PETALS_AMD_MULTI_DECODE={mode!r}: expected one of {', '.join(_MULTI_DECODE_MODES)}"
+        )
+    return mode
+
+
+def set_multi_decode_mode(mode: str) -> None:
+    """Process-wide setter behind Server(multi_decode=...) / --multi_decode."""
+    if mode not in _MULTI_DECODE_MODES:
+        raise ValueError(f"multi_decode={mode!r}: expected one of {', '.join(_MULTI_DECODE_MODES)}")
+    os.environ["PETALS_AMD_MULTI_DECODE"] = mode
+
+
 # Largest row count the `fused` mode sends to the fused kernel, per format:
 # the measured crossover against dequantize + rocBLAS over the llama-2-70b
 # projection shapes (profiles/prefill_gemm_fused.log: NF4 wins everywhere at
@@ -432,6 +458,7 @@ class _TPFastPathMixin:
 
 class LlamaFastPath(_TPFastPathMixin):
     graph_safe = True  # whole-span hipGraph capture is valid for this block
+    multi_decode_supported = True  # decode_multi covers this family's MLP (subclasses say no)
 
     def __init__(self, block, hip_ops, quant: str = "none", tp_world: int = 1, tp_group=None):
         cfg = block.config
@@ -598,6 +625,62 @@ class LlamaFastPath(_TPFastPathMixin):
 
     def _max_gemv_out(self) -> int:
         return max(self.wgateup_t.shape[1], self.wqkv_t.shape[1], self.wo_t.shape[1])
+
+    def multi_decode_eligible(self, batch: int, tokens: int) -> bool:
+        """Steps decode_multi takes: 2..8 tokens, B*T rows within the GEMVs'
+        native batch, one GPU, q heads of a kv head within one MFMA row group."""
+        return (
+            self.multi_decode_supported
+            and 2 <= tokens
+            and batch * tokens <= MULTI_DECODE_MAX_ROWS
+            and self.tp_world == 1
+            and self.gq <= MULTI_DECODE_MAX_GQ
+        )
+
+    @torch.inference_mode()
+    def decode_multi(
+        self,
+        hidden: torch.Tensor,  # [B, T, H] bf16
+        k_cache: torch.Tensor,  # [Bc, KV, Lmax, hd] bf16 or float8_e4m3fn
+        v_cache: torch.Tensor,
+        prefix_length: int,
+    ) -> torch.Tensor:
+        """One step of T = 2..8 new tokens per sequence on the decode kernel
+        chain: decode_step's eight kernels on B*T rows (row b*T + t), every
+        packed weight read once, the T tokens' K/V written at prefix_length ..
+        prefix_length+T-1 and attended causally by attn_decode_multi. No
+        adapter, no tensor parallelism (LlamaBlock.forward routes those to
+        forward())."""
+        B, T, H = hidden.shape
+        if not self.multi_decode_eligible(B, T):
+            raise ValueError(f"decode_multi: step [B={B}, T={T}] (gq={self.gq}, tp={self.tp_world}) is not supported")
+        if prefix_length < 0 or prefix_length + T > k_cache.shape[2] or B > k_cache.shape[0]:
+            raise ValueError(
+                f"decode_multi: positions {prefix_length}..{prefix_length + T - 1} of {B} sequences "
+                f"do not fit a cache of shape {tuple(k_cache.shape)}"
+            )
+        rows = B * T
+        h = hidden.reshape(rows, H)
+        if h.dtype != torch.bfloat16:
+            h = h.to(torch.bfloat16)
+        h = h.contiguous()
+        self._ensure_rope(prefix_length + T)
+        self._pos.fill_(prefix_length)
+        ws = _get_ws(self.device, "gemv", 64 * rows * self._max_gemv_out())
+
+        xn = self.hip.rms_norm_f32out(h, self.ln1_w, self.eps)  # [B*T, H] f32
+        parts = self.wqkv_t.gemv(xn, ws, None, _EPI_RAW)
+        q = self.hip.qkv_rope_reduce_multi(
+            parts, self.rope_cos, self.rope_sin, self._pos, k_cache, v_cache, self.qh, self.kh, T
+        )  # [B*T, qh*hd] f32, rotated; K/V rows written
+        attn = self.hip.attn_decode_multi(
+            q, k_cache, v_cache, self._pos, T, self.gq, 0, self._empty_f32, self._empty_f32, self.scale
+        )  # [B*T, qh*hd] f32
+        h2 = self.wo_t.gemv(attn, ws, h, _EPI_RESIDUAL_BF16)  # [B*T, H] bf16
+        xn2 = self.hip.rms_norm_f32out(h2, self.ln2_w, self.eps)
+        act = self.wgateup_t.gemv(xn2, ws, None, _EPI_SWIGLU_F32)  # [B*T, I] f32
+        h3 = self.wdown_t.gemv(act, ws, h2, _EPI_RESIDUAL_BF16)
+        return h3.view(B, T, H)
 
     def _mlp_decode(self, xn2, h2, ws, adapter):
         if self.tp_world > 1:

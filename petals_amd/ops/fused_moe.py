@@ -158,6 +158,8 @@ class _StackedExperts:
 
 
 class MixtralFastPath(LlamaFastPath):
+    multi_decode_supported = False  # decode_multi runs the dense Llama MLP only
+
     def _init_mlp_weights(self, block, hip_ops, quant):
         def t(w):
             return w.detach().to(torch.bfloat16).t().contiguous()

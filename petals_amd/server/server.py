@@ -86,6 +86,7 @@ class Server:
         tp_group=None,
         prefill_gemm: str = "dense",
         kv_cache_dtype: str = "bf16",
+        multi_decode: str = "off",
     ):
         self.config = load_model_config(model_name_or_dir)
         self.model_name_or_dir = model_name_or_dir
@@ -180,6 +181,17 @@ class Server:
         self.prefill_gemm = prefill_gemm
         if prefill_gemm == "fused":
             set_prefill_gemm_mode("fused")
+        # steps of 2..8 new tokens against the cache (speculative verify) on
+        # Llama blocks: "on" opts this PROCESS into the multi-token decode chain
+        # (ops/csrc/attn_multi.hip); "off" leaves the process setting
+        # (PETALS_AMD_MULTI_DECODE, default off) alone
+        from petals_amd.ops.fused_decode import _MULTI_DECODE_MODES, set_multi_decode_mode
+
+        if multi_decode not in _MULTI_DECODE_MODES:
+            raise ValueError(f"multi_decode={multi_decode!r}: expected one of {_MULTI_DECODE_MODES}")
+        self.multi_decode = multi_decode
+        if multi_decode == "on":
+            set_multi_decode_mode("on")
 
     # -------------------------------------------------------------- sizing
 
