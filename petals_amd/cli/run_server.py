@@ -72,6 +72,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--multi_decode", type=str, default="off", choices=["off", "on"],
                         help="steps of 2..8 new tokens against the KV cache (speculative verify) on Llama "
                              "blocks: the prefill path (off) or the multi-token decode kernel chain (on)")
+    parser.add_argument("--train_attn", type=str, default="torch", choices=["torch", "fused"],
+                        help="attention in rpc_backward on GPU Llama / Mixtral blocks: the torch composition, "
+                             "or the fused flash forward + MFMA backward kernels")
     parser.add_argument("--attn_cache_tokens", type=int, default=16384)
     parser.add_argument("--max_batch_size", type=int, default=8)
     parser.add_argument("--max_chunk_size_bytes", type=int, default=256 * 1024 * 1024,
@@ -167,6 +170,11 @@ def main(argv=None):
 
         set_multi_decode_mode(args.multi_decode)
 
+    if args.train_attn != "torch":
+        from petals_amd.ops import set_train_attn_mode
+
+        set_train_attn_mode(args.train_attn)
+
     if args.tensor_parallel_ranks > 1:
         # launched under torchrun, one process per GPU: rank 0 is the swarm
         # Server; ranks 1.. execute their block shards in lockstep
@@ -243,6 +251,7 @@ def main(argv=None):
         prefill_gemm=args.prefill_gemm,
         kv_cache_dtype=args.kv_cache_dtype,
         multi_decode=args.multi_decode,
+        train_attn=args.train_attn,
     )
     server.start()
     print(f"petals_amd server listening on {server.listen_addr} peer_id={server.peer_id}", flush=True)

@@ -51,7 +51,8 @@ def _require_hip(op_name: str):
 
 def _grad_mode(*tensors) -> bool:
     """True if this op must stay on differentiable torch ops (training path):
-    the HIP kernels are inference-only and would silently break autograd."""
+    the HIP kernels other than FusedCausalAttention are inference-only and
+    would silently break autograd."""
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
@@ -82,10 +83,75 @@ def _alibi_bias_matrix(alibi_slopes, kv_len, device):
     return (alibi_slopes.to(device)[:, None, None] * k_pos[None, None, :]).unsqueeze(0)
 
 
+_TRAIN_ATTN_MODES = ("torch", "fused")
+
+
+def train_attn_mode() -> str:
+    """How attention runs when autograd needs its gradient, read at call time
+    from PETALS_AMD_TRAIN_ATTN: `torch` (default) is the fp32-softmax torch
+    composition with autograd's saved [B, QH, S, S] tensors; `fused` is the
+    LSE flash forward plus the MFMA backward (csrc/attn_bwd.hip), which saves
+    q, k, v, out and one fp32 statistic per row."""
+    mode = os.environ.get("PETALS_AMD_TRAIN_ATTN", "torch")
+    if mode not in _TRAIN_ATTN_MODES:
+        raise ValueError(f"PETALS_AMD_TRAIN_ATTN={mode!r}: expected one of {', '.join(_TRAIN_ATTN_MODES)}")
+    return mode
+
+
+def set_train_attn_mode(mode: str) -> None:
+    """Process-wide setter behind Server(train_attn=...) / --train_attn."""
+    if mode not in _TRAIN_ATTN_MODES:
+        raise ValueError(f"train_attn={mode!r}: expected one of {', '.join(_TRAIN_ATTN_MODES)}")
+    os.environ["PETALS_AMD_TRAIN_ATTN"] = mode
+
+
+class FusedCausalAttention(torch.autograd.Function):
+    """Differentiable causal GQA attention on the HIP kernels: bf16 CUDA
+    q [B, QH, S, HD], k/v [B, KVH, S, HD], head_dim 64/128."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        hops = _require_hip("attention_train")
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out, lse2 = hops.attn_train_fwd(q, k, v, scale)
+        ctx.save_for_backward(q, k, v, out, lse2)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse2 = ctx.saved_tensors
+        hops = _require_hip("attention_train")
+        dq, dk, dv = hops.attn_train_bwd(q, k, v, out, lse2, dout.to(torch.bfloat16).contiguous(), ctx.scale)
+        return dq, dk, dv, None
+
+
+def _fused_train_attention_ok(q, k, v, causal, kv_offset, attn_bias, alibi_slopes) -> bool:
+    return (
+        train_attn_mode() == "fused"
+        and q.is_cuda
+        and causal
+        and kv_offset == 0
+        and attn_bias is None
+        and alibi_slopes is None
+        and q.dtype == k.dtype == v.dtype == torch.bfloat16
+        and q.shape[-1] in (64, 128)
+        and q.shape[1] % k.shape[1] == 0
+        and q.shape[2] == k.shape[2]
+        and _require_hip("attention_train") is not None
+    )
+
+
 def attention(q, k, v, *, causal: bool, kv_offset: int = 0, attn_bias=None, scale=None, alibi_slopes=None):
     """Prefill attention. On GPU (bf16, head_dim 64/128, no additive bias
     matrix — ALiBi via per-head `alibi_slopes` stays on the kernel) this runs
-    the MFMA flash kernel; otherwise the fp32-softmax torch composition."""
+    the MFMA flash kernel; otherwise the fp32-softmax torch composition. With
+    a gradient to carry, the causal no-bias case takes FusedCausalAttention
+    when `train_attn_mode()` is `fused`; everything else stays on torch ops."""
+    if _grad_mode(q, k, v) and _fused_train_attention_ok(q, k, v, causal, kv_offset, attn_bias, alibi_slopes):
+        import math
+
+        return FusedCausalAttention.apply(q, k, v, float(scale) if scale is not None else 1.0 / math.sqrt(q.shape[-1]))
     if (
         q.is_cuda
         and not _grad_mode(q, k, v)

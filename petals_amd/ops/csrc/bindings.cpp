@@ -43,6 +43,10 @@ torch::Tensor attn_prefill_fused(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     int64_t kv_len, int64_t kv_offset, double scale, bool causal,
     c10::optional<torch::Tensor> alibi_slopes);
+std::vector<torch::Tensor> attn_train_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale);
+std::vector<torch::Tensor> attn_train_bwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor out, torch::Tensor lse2,
+    torch::Tensor dout, double scale, int64_t gq_splits);
 std::vector<torch::Tensor> nf4_quantize(torch::Tensor w);
 torch::Tensor gemv_int8(
     torch::Tensor q, torch::Tensor scale, torch::Tensor x, torch::Tensor workspace,
@@ -126,6 +130,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_prefill_fused", &attn_prefill_fused, "MFMA flash prefill attention (bf16, causal, GQA)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kv_len"), py::arg("kv_offset"),
         py::arg("scale"), py::arg("causal"), py::arg("alibi_slopes") = py::none());
+  m.def("attn_train_fwd", &attn_train_fwd,
+        "causal GQA flash forward for training: (out bf16, lse2 f32 [B, QH, S] in the log2 domain)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"));
+  m.def("attn_train_bwd", &attn_train_bwd,
+        "MFMA flash attention backward (two-pass, no atomics): (dq, dk, dv) bf16",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse2"), py::arg("dout"),
+        py::arg("scale"), py::arg("gq_splits") = 0);
   m.def("gemv_int8", &gemv_int8, "split-K weight-only int8 gemv (per-column scales) with epilogue",
         py::arg("q"), py::arg("scale"), py::arg("x"), py::arg("workspace"),
         py::arg("residual"), py::arg("epilogue"), py::arg("splits") = 0, py::arg("bias") = py::none());

@@ -44,7 +44,12 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 // Only the global -> LDS staging loop differs: it loads 8 bytes per chunk and
 // converts them (exactly) to the bf16x8 the bf16 instantiation loads; the LDS
 // images and everything after them are the same.
-template <int HD, bool ALIBI, bool FP8 = false>
+//
+// LSE: the training forward (attn_train_fwd) also writes the per-row softmax
+// statistic lse2 = m + log2(l) in the kernel's own log2 domain, which the
+// backward (attn_bwd.hip) recomputes the probabilities from. The parameter
+// only adds the store after the O write; LSE=false forms ignore `lse`.
+template <int HD, bool ALIBI, bool FP8 = false, bool LSE = false>
 __global__ __launch_bounds__(WAVES * 64) void attn_prefill_kernel(
     const unsigned short* __restrict__ q,   // [B, QH, S, HD]
     const typename std::conditional<FP8, unsigned char, unsigned short>::type* __restrict__ k,  // [B, KVH, Lmax, HD]
@@ -59,7 +64,8 @@ __global__ __launch_bounds__(WAVES * 64) void attn_prefill_kernel(
     int kv_len,     // keys to attend over (cache valid prefix)
     int kv_offset,  // absolute position of q row 0 within the kv sequence
     float scale,
-    int causal) {
+    int causal,
+    float* __restrict__ lse = nullptr) {    // [B, QH, S] f32, LSE only
   constexpr int QR = QTILE;      // q rows per wave
   constexpr int NSET = QR / 16;  // 16-row MFMA row sets per wave
   const int bh = blockIdx.x;          // b * q_heads + qh
@@ -277,6 +283,10 @@ __global__ __launch_bounds__(WAVES * 64) void attn_prefill_kernel(
       unsigned short* dst = out + q_base + (size_t)qrow * HD;
 #pragma unroll
       for (int d = 0; d < HD / 16; ++d) dst[d * 16 + col] = f32_to_bf16(acc_o[qs][d][r] * inv_l);
+      if constexpr (LSE) {
+        // every lane of the row holds the same m and l; causal rows see key 0, so l > 0
+        if (col == 0) lse[((size_t)b * q_heads + qh) * s_q + qrow] = m_row[qs][r] + log2f(l_row[qs][r]);
+      }
     }
 }
 
@@ -335,4 +345,36 @@ torch::Tensor attn_prefill_fused(
 #undef PF_ARGS
   HIP_CHECK_LAST();
   return out;
+}
+
+// Training forward: causal, kv_len == S, kv_offset == 0, bf16, no ALiBi; also
+// returns lse2 [B, QH, S] f32 (log2 domain, scores are (q.k)*scale*log2e).
+std::vector<torch::Tensor> attn_train_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale) {
+  TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16 && q.dim() == 4);
+  TORCH_CHECK(k.scalar_type() == at::kBFloat16 && k.dim() == 4, "k/v must be bf16");
+  TORCH_CHECK(v.scalar_type() == at::kBFloat16 && v.sizes() == k.sizes(), "k and v must share dtype and shape");
+  const int B = q.size(0), QH = q.size(1), S = q.size(2), HD = q.size(3);
+  const int KVH = k.size(1);
+  TORCH_CHECK(k.size(0) == B && k.size(2) == S && k.size(3) == HD, "k/v must be [B, KVH, S, HD]");
+  TORCH_CHECK(HD == 128 || HD == 64, "training attention supports head_dim 64/128");
+  TORCH_CHECK(QH % KVH == 0);
+  TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
+  auto out = torch::empty_like(q);
+  auto lse = torch::empty({B, QH, S}, q.options().dtype(torch::kFloat32));
+  if (q.numel() == 0) return {out, lse};
+  auto stream = at::cuda::getCurrentCUDAStream();
+  dim3 grid(B * QH, (S + WAVES * QTILE - 1) / (WAVES * QTILE));
+  const auto* qp = reinterpret_cast<const unsigned short*>(q.data_ptr());
+  const auto* kp = reinterpret_cast<const unsigned short*>(k.data_ptr());
+  const auto* vp = reinterpret_cast<const unsigned short*>(v.data_ptr());
+  auto* op = reinterpret_cast<unsigned short*>(out.data_ptr());
+  float* lp = lse.data_ptr<float>();
+  if (HD == 128)
+    attn_prefill_kernel<128, false, false, true><<<grid, WAVES * WAVE, 0, stream>>>(
+        qp, kp, vp, op, nullptr, QH, KVH, S, S, S, 0, (float)scale, 1, lp);
+  else
+    attn_prefill_kernel<64, false, false, true><<<grid, WAVES * WAVE, 0, stream>>>(
+        qp, kp, vp, op, nullptr, QH, KVH, S, S, S, 0, (float)scale, 1, lp);
+  HIP_CHECK_LAST();
+  return {out, lse};
 }

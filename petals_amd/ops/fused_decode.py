@@ -110,6 +110,17 @@ def set_prefill_gemm_mode(mode: str) -> None:
     os.environ["PETALS_AMD_PREFILL_GEMM"] = mode
 
 
+def _train_attention(q, k, v):
+    """Causal attention of the training forward: the torch composition, or in
+    `fused` train_attn mode `ops.attention`, which takes the HIP forward and
+    backward where they apply."""
+    from petals_amd import ops
+
+    if ops.train_attn_mode() == "fused":
+        return ops.attention(q, k, v, causal=True)
+    return reference.attention(q, k, v, causal=True)
+
+
 _MULTI_DECODE_MODES = ("off", "on")
 MULTI_DECODE_MAX_ROWS = 8  # B * T rows the GEMVs run natively
 MULTI_DECODE_MAX_GQ = 16  # one 16-row MFMA group holds the q heads of a kv head
@@ -729,7 +740,7 @@ class LlamaFastPath(_TPFastPathMixin):
 
     def forward_autograd(self, hidden: torch.Tensor, prefix_length: int = 0, adapter=None) -> torch.Tensor:
         """Differentiable forward on the transposed weights (torch primitives
-        only — the HIP kernels are inference-only). Used by rpc_backward on GPU
+        only, except attention in `fused` train_attn mode). Used by rpc_backward on GPU
         servers; weights are frozen, grads flow to inputs/prompts."""
         B, S, H = hidden.shape
         end = prefix_length + S
@@ -744,7 +755,7 @@ class LlamaFastPath(_TPFastPathMixin):
         v = qkv[..., (self.qh + self.kh) * self.hd :].view(B, S, self.kh, self.hd).transpose(1, 2)
         pos = torch.arange(prefix_length, end, device=hidden.device)
         q, k = reference.apply_rope(q, k, self.rope_cos, self.rope_sin, pos)
-        attn = reference.attention(q, k, v, causal=True)
+        attn = _train_attention(q, k, v)
         attn = attn.transpose(1, 2).reshape(B, S, self.qh * self.hd).to(hidden.dtype)
         o = self._tp_reduce(torch.matmul(attn, self.wo_t.dense()))
         if adapter is not None:

@@ -87,6 +87,7 @@ class Server:
         prefill_gemm: str = "dense",
         kv_cache_dtype: str = "bf16",
         multi_decode: str = "off",
+        train_attn: str = "torch",
     ):
         self.config = load_model_config(model_name_or_dir)
         self.model_name_or_dir = model_name_or_dir
@@ -192,6 +193,16 @@ class Server:
         self.multi_decode = multi_decode
         if multi_decode == "on":
             set_multi_decode_mode("on")
+        # attention of rpc_backward's re-run forward: "fused" opts this PROCESS
+        # into the LSE flash forward + MFMA backward (ops/csrc/attn_bwd.hip);
+        # "torch" leaves the process setting (PETALS_AMD_TRAIN_ATTN) alone
+        from petals_amd.ops import _TRAIN_ATTN_MODES, set_train_attn_mode
+
+        if train_attn not in _TRAIN_ATTN_MODES:
+            raise ValueError(f"train_attn={train_attn!r}: expected one of {_TRAIN_ATTN_MODES}")
+        self.train_attn = train_attn
+        if train_attn == "fused":
+            set_train_attn_mode("fused")
 
     # -------------------------------------------------------------- sizing
 
