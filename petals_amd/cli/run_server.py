@@ -75,6 +75,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--train_attn", type=str, default="torch", choices=["torch", "fused"],
                         help="attention in rpc_backward on GPU Llama / Mixtral blocks: the torch composition, "
                              "or the fused flash forward + MFMA backward kernels")
+    parser.add_argument("--lora_decode", type=str, default="torch", choices=["torch", "fused"],
+                        help="decode steps under a LoRA adapter on Llama / Mixtral blocks: torch deltas around "
+                             "each GEMV, or the fused shrink + expand-in-the-reduce kernels")
     parser.add_argument("--attn_cache_tokens", type=int, default=16384)
     parser.add_argument("--max_batch_size", type=int, default=8)
     parser.add_argument("--max_chunk_size_bytes", type=int, default=256 * 1024 * 1024,
@@ -175,6 +178,11 @@ def main(argv=None):
 
         set_train_attn_mode(args.train_attn)
 
+    if args.lora_decode != "torch":
+        from petals_amd.ops.fused_decode import set_lora_decode_mode
+
+        set_lora_decode_mode(args.lora_decode)
+
     if args.tensor_parallel_ranks > 1:
         # launched under torchrun, one process per GPU: rank 0 is the swarm
         # Server; ranks 1.. execute their block shards in lockstep
@@ -252,6 +260,7 @@ def main(argv=None):
         kv_cache_dtype=args.kv_cache_dtype,
         multi_decode=args.multi_decode,
         train_attn=args.train_attn,
+        lora_decode=args.lora_decode,
     )
     server.start()
     print(f"petals_amd server listening on {server.listen_addr} peer_id={server.peer_id}", flush=True)

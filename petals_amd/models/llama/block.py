@@ -205,13 +205,23 @@ class LlamaBlock(nn.Module):
                     self._fast, hidden_states, kv_cache[0], kv_cache[1], prefix_length,
                     ctx=ctx, adapter=adapter,
                 )
-            if kv_cache is not None and adapter is None and hidden_states.shape[1] >= 2:
+            if kv_cache is not None and hidden_states.shape[1] >= 2:
                 from petals_amd.ops.fused_decode import multi_decode_mode
+                from petals_amd.ops.lora import lora_fused_eligible
 
                 # opt-in (PETALS_AMD_MULTI_DECODE=on): a short multi-token step,
-                # e.g. a speculative verify, on the decode kernel chain
-                if multi_decode_mode() == "on" and self._fast.multi_decode_eligible(*hidden_states.shape[:2]):
-                    return self._fast.decode_multi(hidden_states, kv_cache[0], kv_cache[1], prefix_length)
+                # e.g. a speculative verify, on the decode kernel chain; under
+                # an adapter only with the fused LoRA kernels
+                # (PETALS_AMD_LORA_DECODE=fused)
+                b, t = hidden_states.shape[:2]
+                if (
+                    multi_decode_mode() == "on"
+                    and self._fast.multi_decode_eligible(b, t)
+                    and (adapter is None or lora_fused_eligible(self._fast, adapter, b * t))
+                ):
+                    return self._fast.decode_multi(
+                        hidden_states, kv_cache[0], kv_cache[1], prefix_length, adapter=adapter
+                    )
             return self._fast.forward(hidden_states, kv_cache, prefix_length, adapter=adapter)
 
         from petals_amd.utils.peft import active_block_adapter

@@ -86,6 +86,11 @@ torch::Tensor gemv_mxfp4(
 int64_t gemv_mxfp4_splits(int64_t in_dim, int64_t out_dim, int64_t batch, int64_t splits_override);
 torch::Tensor gemm_mxfp4(
     torch::Tensor packed, torch::Tensor scales, torch::Tensor x, c10::optional<torch::Tensor> bias);
+torch::Tensor lora_shrink(torch::Tensor x, torch::Tensor a_cat);
+torch::Tensor lora_reduce(
+    torch::Tensor partials, torch::Tensor t_part, torch::Tensor bt, std::vector<int64_t> segments,
+    std::vector<double> scales, c10::optional<torch::Tensor> residual, c10::optional<torch::Tensor> bias,
+    int64_t epilogue);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rms_norm", &rms_norm, "RMSNorm (bf16 -> bf16)");
@@ -190,4 +195,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dense prefill MFMA GEMM x[M,in] @ MXFP4 W[in,out] (+bias) -> bf16, hardware fp4 dequant "
         "fused into the LDS staging",
         py::arg("packed"), py::arg("scales"), py::arg("x"), py::arg("bias") = py::none());
+  m.def("lora_shrink", &lora_shrink,
+        "LoRA shrink for decode: x f32 [rows <= 8, in] . a_cat bf16 [R <= 256, in] -> split-K "
+        "partials f32 [S, rows, R] (deterministic, no atomics)",
+        py::arg("x"), py::arg("a_cat"));
+  m.def("lora_reduce", &lora_reduce,
+        "split-K reduce of RAW gemv partials with the LoRA expand folded in before the epilogue "
+        "(plain f32, residual bf16, swiglu f32); segments hold (c0, c1, t_off, rank, bt_off) per member",
+        py::arg("partials"), py::arg("t_part"), py::arg("bt"), py::arg("segments"), py::arg("scales"),
+        py::arg("residual") = py::none(), py::arg("bias") = py::none(), py::arg("epilogue") = 0);
 }

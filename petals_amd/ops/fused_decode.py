@@ -28,6 +28,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
+from petals_amd.ops import lora as _lora
 from petals_amd.ops import reference
 
 _EPI_RAW = -1  # return split partials; caller fuses its own reduce+epilogue
@@ -145,6 +146,30 @@ def set_multi_decode_mode(mode: str) -> None:
     if mode not in _MULTI_DECODE_MODES:
         raise ValueError(f"multi_decode={mode!r}: expected one of {', '.join(_MULTI_DECODE_MODES)}")
     os.environ["PETALS_AMD_MULTI_DECODE"] = mode
+
+
+_LORA_DECODE_MODES = ("torch", "fused")
+
+
+def lora_decode_mode() -> str:
+    """How the Llama / Mixtral decode chain serves an active LoRA adapter, read
+    at call time from PETALS_AMD_LORA_DECODE: `torch` (default) adds
+    BlockAdapter.delta around each GEMV; `fused` runs every projection group
+    as base GEMV -> lora_shrink -> lora_reduce (ops/lora.py, csrc/lora.hip)
+    when ops.lora.lora_fused_eligible holds."""
+    mode = os.environ.get("PETALS_AMD_LORA_DECODE", "torch")
+    if mode not in _LORA_DECODE_MODES:
+        raise ValueError(
+            f"PETALS_AMD_LORA_DECODE={mode!r}: expected one of {', '.join(_LORA_DECODE_MODES)}"
+        )
+    return mode
+
+
+def set_lora_decode_mode(mode: str) -> None:
+    """Process-wide setter behind Server(lora_decode=...) / --lora_decode."""
+    if mode not in _LORA_DECODE_MODES:
+        raise ValueError(f"lora_decode={mode!r}: expected one of {', '.join(_LORA_DECODE_MODES)}")
+    os.environ["PETALS_AMD_LORA_DECODE"] = mode
 
 
 # Largest row count the `fused` mode sends to the fused kernel, per format:
@@ -599,8 +624,15 @@ class LlamaFastPath(_TPFastPathMixin):
             pos, kv_len = ctx.pos, ctx.kv_len
         ws = _get_ws(self.device, "gemv", 64 * B * self._max_gemv_out())
 
-        if adapter is None:
-            xn = self.hip.rms_norm_f32out(h, self.ln1_w, self.eps)  # [B, H] f32
+        lora_fused = adapter is not None and _lora.lora_fused_eligible(self, adapter, B)
+        xn = self.hip.rms_norm_f32out(h, self.ln1_w, self.eps)  # [B, H] f32
+        qkv = None
+        if lora_fused:  # None when the adapter has nothing on q, k, v
+            qkv = self._lora_group("qkv", self.wqkv_t, xn, ws, adapter, None, _EPI_PLAIN_F32)
+        elif adapter is not None:
+            qkv = self.wqkv_t.gemv(xn, ws, None, _EPI_PLAIN_F32)  # [B, qkv] f32
+            self._apply_qkv_adapter(qkv, xn, adapter)
+        if qkv is None:
             # fused qkv reduce + rope + cache write: one kernel fewer per block
             parts = self.wqkv_t.gemv(xn, ws, None, _EPI_RAW)
             q = self.hip.qkv_rope_reduce(
@@ -608,9 +640,6 @@ class LlamaFastPath(_TPFastPathMixin):
                 self.qh, self.kh, True,
             )  # [B, qh*hd] f32, rotated
         else:
-            xn = self.hip.rms_norm_f32out(h, self.ln1_w, self.eps)
-            qkv = self.wqkv_t.gemv(xn, ws, None, _EPI_PLAIN_F32)  # [B, qkv] f32
-            self._apply_qkv_adapter(qkv, xn, adapter)
             self.hip.rope_cache_write(
                 qkv, self.rope_cos, self.rope_sin, pos, k_cache[:B], v_cache[:B], self.qh, self.kh
             )
@@ -623,6 +652,10 @@ class LlamaFastPath(_TPFastPathMixin):
             part = self.wo_t.gemv(attn, ws, None, _EPI_PLAIN_F32)  # [B, H] f32 partial
             self._tp_allreduce_(part)
             h2 = (h.float() + part).to(torch.bfloat16)
+        elif lora_fused:
+            h2 = self._lora_group("o", self.wo_t, attn, ws, adapter, h, _EPI_RESIDUAL_BF16)
+            if h2 is None:
+                h2 = self.wo_t.gemv(attn, ws, h, _EPI_RESIDUAL_BF16)
         elif adapter is not None:
             d = adapter.delta("o", attn)
             h2 = self.wo_t.gemv(attn, ws, h, _EPI_RESIDUAL_BF16)  # [B, H] bf16
@@ -636,6 +669,29 @@ class LlamaFastPath(_TPFastPathMixin):
 
     def _max_gemv_out(self) -> int:
         return max(self.wgateup_t.shape[1], self.wqkv_t.shape[1], self.wo_t.shape[1])
+
+    def _lora_members(self, group: str):
+        """(projection key, c0, c1) of a group's members in its fused output."""
+        if group == "qkv":
+            qd, kd = self.qh * self.hd, self.kh * self.hd
+            return (("q", 0, qd), ("k", qd, qd + kd), ("v", qd + kd, qd + 2 * kd))
+        if group == "gateup":
+            inter = self.wgateup_t.shape[1] // 2
+            return (("gate", 0, inter), ("up", inter, 2 * inter))
+        return ((group, 0, (self.wo_t if group == "o" else self.wdown_t).shape[1]),)
+
+    def _lora_group(self, group, w, x, ws, adapter, residual, epilogue):
+        """One projection group under a fused-eligible adapter: the base GEMV's
+        raw split partials (in `ws`, as for qkv_rope_reduce), the shrink
+        x . A^T, and the reduce that adds scale * t . B^T before the epilogue.
+        None when the adapter has no member in the group: the caller keeps the
+        adapter-free kernel."""
+        pack = _lora.get_pack(self, adapter, group, self._lora_members(group))
+        if pack is None:
+            return None
+        parts = w.gemv(x, ws, None, _EPI_RAW)
+        t_part = self.hip.lora_shrink(x, pack.a_cat)
+        return self.hip.lora_reduce(parts, t_part, pack.bt, pack.segments, pack.scales, residual, None, epilogue)
 
     def multi_decode_eligible(self, batch: int, tokens: int) -> bool:
         """Steps decode_multi takes: 2..8 tokens, B*T rows within the GEMVs'
@@ -655,16 +711,20 @@ class LlamaFastPath(_TPFastPathMixin):
         k_cache: torch.Tensor,  # [Bc, KV, Lmax, hd] bf16 or float8_e4m3fn
         v_cache: torch.Tensor,
         prefix_length: int,
+        adapter=None,
     ) -> torch.Tensor:
         """One step of T = 2..8 new tokens per sequence on the decode kernel
         chain: decode_step's eight kernels on B*T rows (row b*T + t), every
         packed weight read once, the T tokens' K/V written at prefix_length ..
-        prefix_length+T-1 and attended causally by attn_decode_multi. No
-        adapter, no tensor parallelism (LlamaBlock.forward routes those to
-        forward())."""
+        prefix_length+T-1 and attended causally by attn_decode_multi. An
+        adapter must be fused-eligible on B*T rows (ops/lora.py): its groups
+        run the three-kernel LoRA form. No tensor parallelism
+        (LlamaBlock.forward routes everything else to forward())."""
         B, T, H = hidden.shape
         if not self.multi_decode_eligible(B, T):
             raise ValueError(f"decode_multi: step [B={B}, T={T}] (gq={self.gq}, tp={self.tp_world}) is not supported")
+        if adapter is not None and not _lora.lora_fused_eligible(self, adapter, B * T):
+            raise ValueError("decode_multi: the adapter is not eligible for the fused LoRA decode kernels")
         if prefix_length < 0 or prefix_length + T > k_cache.shape[2] or B > k_cache.shape[0]:
             raise ValueError(
                 f"decode_multi: positions {prefix_length}..{prefix_length + T - 1} of {B} sequences "
@@ -680,17 +740,29 @@ class LlamaFastPath(_TPFastPathMixin):
         ws = _get_ws(self.device, "gemv", 64 * rows * self._max_gemv_out())
 
         xn = self.hip.rms_norm_f32out(h, self.ln1_w, self.eps)  # [B*T, H] f32
-        parts = self.wqkv_t.gemv(xn, ws, None, _EPI_RAW)
-        q = self.hip.qkv_rope_reduce_multi(
-            parts, self.rope_cos, self.rope_sin, self._pos, k_cache, v_cache, self.qh, self.kh, T
-        )  # [B*T, qh*hd] f32, rotated; K/V rows written
+        qkv = None
+        if adapter is not None:
+            qkv = self._lora_group("qkv", self.wqkv_t, xn, ws, adapter, None, _EPI_PLAIN_F32)
+        if qkv is not None:
+            self.hip.rope_cache_write_multi(
+                qkv, self.rope_cos, self.rope_sin, self._pos, k_cache, v_cache, self.qh, self.kh, T
+            )
+            q = qkv[:, : self.qh * self.hd].contiguous()
+        else:
+            parts = self.wqkv_t.gemv(xn, ws, None, _EPI_RAW)
+            q = self.hip.qkv_rope_reduce_multi(
+                parts, self.rope_cos, self.rope_sin, self._pos, k_cache, v_cache, self.qh, self.kh, T
+            )  # [B*T, qh*hd] f32, rotated; K/V rows written
         attn = self.hip.attn_decode_multi(
             q, k_cache, v_cache, self._pos, T, self.gq, 0, self._empty_f32, self._empty_f32, self.scale
         )  # [B*T, qh*hd] f32
-        h2 = self.wo_t.gemv(attn, ws, h, _EPI_RESIDUAL_BF16)  # [B*T, H] bf16
+        h2 = None
+        if adapter is not None:
+            h2 = self._lora_group("o", self.wo_t, attn, ws, adapter, h, _EPI_RESIDUAL_BF16)
+        if h2 is None:
+            h2 = self.wo_t.gemv(attn, ws, h, _EPI_RESIDUAL_BF16)  # [B*T, H] bf16
         xn2 = self.hip.rms_norm_f32out(h2, self.ln2_w, self.eps)
-        act = self.wgateup_t.gemv(xn2, ws, None, _EPI_SWIGLU_F32)  # [B*T, I] f32
-        h3 = self.wdown_t.gemv(act, ws, h2, _EPI_RESIDUAL_BF16)
+        h3 = self._mlp_decode(xn2, h2, ws, adapter)  # adapter None: the two fused-epilogue GEMVs
         return h3.view(B, T, H)
 
     def _mlp_decode(self, xn2, h2, ws, adapter):
@@ -703,6 +775,12 @@ class LlamaFastPath(_TPFastPathMixin):
         if adapter is None:
             act = self.wgateup_t.gemv(xn2, ws, None, _EPI_SWIGLU_F32)  # [B, I] f32
             return self.wdown_t.gemv(act, ws, h2, _EPI_RESIDUAL_BF16)
+        if _lora.lora_fused_eligible(self, adapter, xn2.shape[0]):
+            act = self._lora_group("gateup", self.wgateup_t, xn2, ws, adapter, None, _EPI_SWIGLU_F32)
+            if act is None:
+                act = self.wgateup_t.gemv(xn2, ws, None, _EPI_SWIGLU_F32)
+            h3 = self._lora_group("down", self.wdown_t, act, ws, adapter, h2, _EPI_RESIDUAL_BF16)
+            return h3 if h3 is not None else self.wdown_t.gemv(act, ws, h2, _EPI_RESIDUAL_BF16)
         gateup = self.wgateup_t.gemv(xn2, ws, None, _EPI_PLAIN_F32)  # [B, 2I] f32
         inter = self.wgateup_t.shape[1] // 2
         dg, du = adapter.delta("gate", xn2), adapter.delta("up", xn2)

@@ -88,6 +88,7 @@ class Server:
         kv_cache_dtype: str = "bf16",
         multi_decode: str = "off",
         train_attn: str = "torch",
+        lora_decode: str = "torch",
     ):
         self.config = load_model_config(model_name_or_dir)
         self.model_name_or_dir = model_name_or_dir
@@ -203,6 +204,17 @@ class Server:
         self.train_attn = train_attn
         if train_attn == "fused":
             set_train_attn_mode("fused")
+        # decode steps under an active LoRA adapter on Llama / Mixtral blocks:
+        # "fused" opts this PROCESS into the shrink + expand-in-the-reduce
+        # kernels (ops/csrc/lora.hip); "torch" leaves the process setting
+        # (PETALS_AMD_LORA_DECODE, default torch) alone
+        from petals_amd.ops.fused_decode import _LORA_DECODE_MODES, set_lora_decode_mode
+
+        if lora_decode not in _LORA_DECODE_MODES:
+            raise ValueError(f"lora_decode={lora_decode!r}: expected one of {_LORA_DECODE_MODES}")
+        self.lora_decode = lora_decode
+        if lora_decode == "fused":
+            set_lora_decode_mode("fused")
 
     # -------------------------------------------------------------- sizing
 

@@ -70,6 +70,7 @@ class BlockAdapter:
             k: (a.to(device=device, dtype=dtype), b.to(device=device, dtype=dtype), s)
             for k, (a, b, s) in self.projections.items()
         }
+        self.__dict__.pop("_lora_cache", None)  # fused-decode packs (ops/lora.py) hold the old tensors
         return self
 
     def delta(self, key: str, x: torch.Tensor) -> Optional[torch.Tensor]:
