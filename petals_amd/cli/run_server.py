@@ -78,6 +78,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--lora_decode", type=str, default="torch", choices=["torch", "fused"],
                         help="decode steps under a LoRA adapter on Llama / Mixtral blocks: torch deltas around "
                              "each GEMV, or the fused shrink + expand-in-the-reduce kernels")
+    parser.add_argument("--wide_decode", type=str, default="off", choices=["off", "on"],
+                        help="decode and multi-token steps of 9..32 rows on NF4 Llama blocks: the prefill path "
+                             "(off) or the decode kernel chain on the skinny-M MFMA kernel (on)")
     parser.add_argument("--attn_cache_tokens", type=int, default=16384)
     parser.add_argument("--max_batch_size", type=int, default=8)
     parser.add_argument("--max_chunk_size_bytes", type=int, default=256 * 1024 * 1024,
@@ -183,6 +186,11 @@ def main(argv=None):
 
         set_lora_decode_mode(args.lora_decode)
 
+    if args.wide_decode != "off":
+        from petals_amd.ops.fused_decode import set_wide_decode_mode
+
+        set_wide_decode_mode(args.wide_decode)
+
     if args.tensor_parallel_ranks > 1:
         # launched under torchrun, one process per GPU: rank 0 is the swarm
         # Server; ranks 1.. execute their block shards in lockstep
@@ -261,6 +269,7 @@ def main(argv=None):
         multi_decode=args.multi_decode,
         train_attn=args.train_attn,
         lora_decode=args.lora_decode,
+        wide_decode=args.wide_decode,
     )
     server.start()
     print(f"petals_amd server listening on {server.listen_addr} peer_id={server.peer_id}", flush=True)

@@ -205,6 +205,16 @@ class LlamaBlock(nn.Module):
                     self._fast, hidden_states, kv_cache[0], kv_cache[1], prefix_length,
                     ctx=ctx, adapter=adapter,
                 )
+            if (
+                kv_cache is not None
+                and hidden_states.shape[1] == 1
+                and self._fast.wide_decode_eligible(hidden_states.shape[0], adapter)
+            ):
+                # opt-in (PETALS_AMD_WIDE_DECODE=on): 9..32 sequences on the
+                # decode kernel chain, NF4 projections on the skinny-M kernel
+                return self._fast.decode_step(
+                    hidden_states, kv_cache[0], kv_cache[1], prefix_length, ctx=ctx
+                )
             if kv_cache is not None and hidden_states.shape[1] >= 2:
                 from petals_amd.ops.fused_decode import multi_decode_mode
                 from petals_amd.ops.lora import lora_fused_eligible
@@ -216,7 +226,7 @@ class LlamaBlock(nn.Module):
                 b, t = hidden_states.shape[:2]
                 if (
                     multi_decode_mode() == "on"
-                    and self._fast.multi_decode_eligible(b, t)
+                    and self._fast.multi_decode_eligible(b, t, adapter)
                     and (adapter is None or lora_fused_eligible(self._fast, adapter, b * t))
                 ):
                     return self._fast.decode_multi(

@@ -3,7 +3,7 @@
 `LlamaFastPath` repacks a loaded LlamaBlock's weights into kernel-optimal
 layout (transposed [in, out] bf16, QKV and gate/up concatenated) and then runs:
 
-  decode (q_len == 1, any batch <= 8):
+  decode (q_len == 1, any batch <= 8; NF4 with PETALS_AMD_WIDE_DECODE=on: <= 32):
       rms_norm_f32out -> gemv(QKV) -> rope_cache_write -> attn_decode_fused
       -> gemv(O, +residual) -> rms_norm_f32out -> gemv(gate|up, SwiGLU epi)
       -> gemv(down, +residual)
@@ -170,6 +170,31 @@ def set_lora_decode_mode(mode: str) -> None:
     if mode not in _LORA_DECODE_MODES:
         raise ValueError(f"lora_decode={mode!r}: expected one of {', '.join(_LORA_DECODE_MODES)}")
     os.environ["PETALS_AMD_LORA_DECODE"] = mode
+
+
+_WIDE_DECODE_MODES = ("off", "on")
+WIDE_DECODE_MAX_ROWS = 32  # rows gemm_nf4_skinny takes: two 16-row MFMA groups
+
+
+def wide_decode_mode() -> str:
+    """How an NF4 Llama block runs a decode or multi-token step of 9..32 rows,
+    read at call time from PETALS_AMD_WIDE_DECODE: `off` (default) is the
+    prefill path (LlamaFastPath.forward); `on` is the decode kernel chain with
+    every projection on the skinny-M MFMA kernel (csrc/nf4_skinny.hip), see
+    LlamaFastPath.wide_decode_eligible."""
+    mode = os.environ.get("PETALS_AMD_WIDE_DECODE", "off")
+    if mode not in _WIDE_DECODE_MODES:
+        raise ValueError(
+            f"PETALS_AMD_WIDE_DECODE={mode!r}: expected one of {', '.join(_WIDE_DECODE_MODES)}"
+        )
+    return mode
+
+
+def set_wide_decode_mode(mode: str) -> None:
+    """Process-wide setter behind Server(wide_decode=...) / --wide_decode."""
+    if mode not in _WIDE_DECODE_MODES:
+        raise ValueError(f"wide_decode={mode!r}: expected one of {', '.join(_WIDE_DECODE_MODES)}")
+    os.environ["PETALS_AMD_WIDE_DECODE"] = mode
 
 
 # Largest row count the `fused` mode sends to the fused kernel, per format:
@@ -341,6 +366,10 @@ class _FastWeight:
         return self.hip.gemv_bf16(self.t, x, ws, residual, epilogue, splits, bias)
 
     def gemv(self, x, ws, residual, epilogue, bias=None):
+        if self.quant == "nf4" and 8 < x.shape[0] <= WIDE_DECODE_MAX_ROWS:
+            # 9..32 rows: the skinny-M MFMA kernel, same partials and epilogues
+            return self.hip.gemm_nf4_skinny(self.packed, self.absmax, x, ws, residual, epilogue, 0, bias,
+                                            self.absmax_t)
         if self.quant == "nf4" and self.wg_waves > 1 and x.shape[0] <= _NF4_WG_MAX_BATCH:
             return self.hip.gemv_nf4(self.packed, self.absmax, x, ws, residual, epilogue, self.splits, bias,
                                      self.absmax_t, self.wg_waves, self.nt)
@@ -622,7 +651,10 @@ class LlamaFastPath(_TPFastPathMixin):
             # already cover the cache (ensure_rope(lmax) at session start)
             self._ensure_rope(k_cache.shape[2])
             pos, kv_len = ctx.pos, ctx.kv_len
-        ws = _get_ws(self.device, "gemv", 64 * B * self._max_gemv_out())
+        if B > 8 and not self.wide_decode_eligible(B, adapter):
+            raise ValueError(f"decode_step: {B} rows need PETALS_AMD_WIDE_DECODE=on, NF4 weights, one GPU, no adapter")
+        # wide steps (9..32 rows) keep S * rows <= 512 partial rows: the 8-row request covers them
+        ws = _get_ws(self.device, "gemv", 64 * min(B, 8) * self._max_gemv_out())
 
         lora_fused = adapter is not None and _lora.lora_fused_eligible(self, adapter, B)
         xn = self.hip.rms_norm_f32out(h, self.ln1_w, self.eps)  # [B, H] f32
@@ -693,13 +725,28 @@ class LlamaFastPath(_TPFastPathMixin):
         t_part = self.hip.lora_shrink(x, pack.a_cat)
         return self.hip.lora_reduce(parts, t_part, pack.bt, pack.segments, pack.scales, residual, None, epilogue)
 
-    def multi_decode_eligible(self, batch: int, tokens: int) -> bool:
+    def wide_decode_eligible(self, rows: int, adapter=None) -> bool:
+        """Steps of 9..32 rows the decode chain takes: wide mode on, every
+        weight NF4 (gemm_nf4_skinny), the dense Llama MLP, one GPU, no adapter
+        (lora_shrink / lora_reduce stop at 8 rows)."""
+        return (
+            8 < rows <= WIDE_DECODE_MAX_ROWS
+            and self.quant == "nf4"
+            and self.multi_decode_supported
+            and self.tp_world == 1
+            and adapter is None
+            and wide_decode_mode() == "on"
+        )
+
+    def multi_decode_eligible(self, batch: int, tokens: int, adapter=None) -> bool:
         """Steps decode_multi takes: 2..8 tokens, B*T rows within the GEMVs'
-        native batch, one GPU, q heads of a kv head within one MFMA row group."""
+        native batch (or within the wide cap, wide_decode_eligible), one GPU,
+        q heads of a kv head within one MFMA row group."""
+        rows = batch * tokens
         return (
             self.multi_decode_supported
-            and 2 <= tokens
-            and batch * tokens <= MULTI_DECODE_MAX_ROWS
+            and 2 <= tokens <= 8
+            and (rows <= MULTI_DECODE_MAX_ROWS or self.wide_decode_eligible(rows, adapter))
             and self.tp_world == 1
             and self.gq <= MULTI_DECODE_MAX_GQ
         )
@@ -721,7 +768,7 @@ class LlamaFastPath(_TPFastPathMixin):
         run the three-kernel LoRA form. No tensor parallelism
         (LlamaBlock.forward routes everything else to forward())."""
         B, T, H = hidden.shape
-        if not self.multi_decode_eligible(B, T):
+        if not self.multi_decode_eligible(B, T, adapter):
             raise ValueError(f"decode_multi: step [B={B}, T={T}] (gq={self.gq}, tp={self.tp_world}) is not supported")
         if adapter is not None and not _lora.lora_fused_eligible(self, adapter, B * T):
             raise ValueError("decode_multi: the adapter is not eligible for the fused LoRA decode kernels")
@@ -737,7 +784,7 @@ class LlamaFastPath(_TPFastPathMixin):
         h = h.contiguous()
         self._ensure_rope(prefix_length + T)
         self._pos.fill_(prefix_length)
-        ws = _get_ws(self.device, "gemv", 64 * rows * self._max_gemv_out())
+        ws = _get_ws(self.device, "gemv", 64 * min(rows, 8) * self._max_gemv_out())
 
         xn = self.hip.rms_norm_f32out(h, self.ln1_w, self.eps)  # [B*T, H] f32
         qkv = None

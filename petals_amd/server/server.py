@@ -89,6 +89,7 @@ class Server:
         multi_decode: str = "off",
         train_attn: str = "torch",
         lora_decode: str = "torch",
+        wide_decode: str = "off",
     ):
         self.config = load_model_config(model_name_or_dir)
         self.model_name_or_dir = model_name_or_dir
@@ -215,6 +216,17 @@ class Server:
         self.lora_decode = lora_decode
         if lora_decode == "fused":
             set_lora_decode_mode("fused")
+        # decode and multi-token steps of 9..32 rows on NF4 Llama blocks: "on"
+        # opts this PROCESS into the decode chain on the skinny-M MFMA kernel
+        # (ops/csrc/nf4_skinny.hip); "off" leaves the process setting
+        # (PETALS_AMD_WIDE_DECODE, default off) alone
+        from petals_amd.ops.fused_decode import _WIDE_DECODE_MODES, set_wide_decode_mode
+
+        if wide_decode not in _WIDE_DECODE_MODES:
+            raise ValueError(f"wide_decode={wide_decode!r}: expected one of {_WIDE_DECODE_MODES}")
+        self.wide_decode = wide_decode
+        if wide_decode == "on":
+            set_wide_decode_mode("on")
 
     # -------------------------------------------------------------- sizing
 
