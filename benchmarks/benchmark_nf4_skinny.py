@@ -81,7 +81,7 @@ def bench_gemm(hip, name, in_dim, out_dim, iters, warmup, repeats, rotate_mb, se
     return out
 
 
-def bench_block(model, iters, warmup, repeats):
+def bench_block(model, iters, warmup, repeats, quant="nf4"):
     from petals_amd.models.config_base import load_model_config
     from petals_amd.ops import fused_decode
     from petals_amd.server.from_pretrained import build_empty_block, init_random_block_
@@ -89,7 +89,7 @@ def bench_block(model, iters, warmup, repeats):
     cfg = load_model_config(model)
     blk = build_empty_block(cfg, 0, "cuda:0", torch.bfloat16)
     init_random_block_(blk, cfg, 0)
-    blk = blk.eval().optimize_for_inference(quant="nf4")
+    blk = blk.eval().optimize_for_inference(quant=quant)
     fast = blk._fast
 
     def empty_lru():
@@ -125,7 +125,7 @@ def bench_block(model, iters, warmup, repeats):
             us = {name: _median(m) for name, m in meds.items()}
             spread = {name: (min(m), max(m)) for name, m in meds.items()}
             out.append(dict(model=model, B=B, kv=kv, us=us, spread=spread))
-            print(f"block {model} B={B:2d} kv={kv:4d}  "
+            print(f"block {model} {quant} B={B:2d} kv={kv:4d}  "
                   + "  ".join(f"{name} {us[name]:8.1f} [{spread[name][0]:.1f}..{spread[name][1]:.1f}] us" for name in runs),
                   flush=True)
     empty_lru()

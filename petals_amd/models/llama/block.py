@@ -211,7 +211,8 @@ class LlamaBlock(nn.Module):
                 and self._fast.wide_decode_eligible(hidden_states.shape[0], adapter)
             ):
                 # opt-in (PETALS_AMD_WIDE_DECODE=on): 9..32 sequences on the
-                # decode kernel chain, NF4 projections on the skinny-M kernel
+                # decode kernel chain, NF4 or MXFP4 projections on the format's
+                # skinny-M kernel
                 return self._fast.decode_step(
                     hidden_states, kv_cache[0], kv_cache[1], prefix_length, ctx=ctx
                 )

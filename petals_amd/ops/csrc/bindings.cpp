@@ -91,6 +91,11 @@ torch::Tensor gemm_nf4_skinny(
     c10::optional<torch::Tensor> residual, int64_t epilogue, int64_t splits_override,
     c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> absmax_t);
 int64_t gemm_nf4_skinny_splits(int64_t in_dim, int64_t out_dim, int64_t rows, int64_t splits_override);
+torch::Tensor gemm_mxfp4_skinny(
+    torch::Tensor packed, torch::Tensor scales, torch::Tensor x, torch::Tensor workspace,
+    c10::optional<torch::Tensor> residual, int64_t epilogue, int64_t splits_override,
+    c10::optional<torch::Tensor> bias);
+int64_t gemm_mxfp4_skinny_splits(int64_t in_dim, int64_t out_dim, int64_t rows, int64_t splits_override);
 torch::Tensor lora_shrink(torch::Tensor x, torch::Tensor a_cat);
 torch::Tensor lora_reduce(
     torch::Tensor partials, torch::Tensor t_part, torch::Tensor bt, std::vector<int64_t> segments,
@@ -208,6 +213,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none(), py::arg("absmax_t") = py::none());
   m.def("gemm_nf4_skinny_splits", &gemm_nf4_skinny_splits,
         "split count gemm_nf4_skinny uses for a shape (S * rows <= 512)",
+        py::arg("in_dim"), py::arg("out_dim"), py::arg("rows"), py::arg("splits") = 0);
+  m.def("gemm_mxfp4_skinny", &gemm_mxfp4_skinny,
+        "wide decode: x f32 [9..32 rows, in] @ MXFP4 W[in,out], weight streamed once through MFMA "
+        "(hardware fp4 -> bf16 dequant), split-K partials [S, rows, out] + the gemv epilogues "
+        "(epilogue < 0: raw partials)",
+        py::arg("packed"), py::arg("scales"), py::arg("x"), py::arg("workspace"),
+        py::arg("residual") = py::none(), py::arg("epilogue") = 0, py::arg("splits") = 0,
+        py::arg("bias") = py::none());
+  m.def("gemm_mxfp4_skinny_splits", &gemm_mxfp4_skinny_splits,
+        "split count gemm_mxfp4_skinny uses for a shape (S * rows <= 512)",
         py::arg("in_dim"), py::arg("out_dim"), py::arg("rows"), py::arg("splits") = 0);
   m.def("lora_shrink", &lora_shrink,
         "LoRA shrink for decode: x f32 [rows <= 8, in] . a_cat bf16 [R <= 256, in] -> split-K "

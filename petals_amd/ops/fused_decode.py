@@ -3,7 +3,7 @@
 `LlamaFastPath` repacks a loaded LlamaBlock's weights into kernel-optimal
 layout (transposed [in, out] bf16, QKV and gate/up concatenated) and then runs:
 
-  decode (q_len == 1, any batch <= 8; NF4 with PETALS_AMD_WIDE_DECODE=on: <= 32):
+  decode (q_len == 1, any batch <= 8; NF4 / MXFP4 with PETALS_AMD_WIDE_DECODE=on: <= 32):
       rms_norm_f32out -> gemv(QKV) -> rope_cache_write -> attn_decode_fused
       -> gemv(O, +residual) -> rms_norm_f32out -> gemv(gate|up, SwiGLU epi)
       -> gemv(down, +residual)
@@ -173,14 +173,15 @@ def set_lora_decode_mode(mode: str) -> None:
 
 
 _WIDE_DECODE_MODES = ("off", "on")
-WIDE_DECODE_MAX_ROWS = 32  # rows gemm_nf4_skinny takes: two 16-row MFMA groups
+WIDE_DECODE_MAX_ROWS = 32  # rows gemm_nf4_skinny / gemm_mxfp4_skinny take: two 16-row MFMA groups
 
 
 def wide_decode_mode() -> str:
-    """How an NF4 Llama block runs a decode or multi-token step of 9..32 rows,
-    read at call time from PETALS_AMD_WIDE_DECODE: `off` (default) is the
-    prefill path (LlamaFastPath.forward); `on` is the decode kernel chain with
-    every projection on the skinny-M MFMA kernel (csrc/nf4_skinny.hip), see
+    """How an NF4 or MXFP4 Llama block runs a decode or multi-token step of
+    9..32 rows, read at call time from PETALS_AMD_WIDE_DECODE: `off` (default)
+    is the prefill path (LlamaFastPath.forward); `on` is the decode kernel
+    chain with every projection on the format's skinny-M MFMA kernel
+    (csrc/nf4_skinny.hip, csrc/mxfp4_skinny.hip), see
     LlamaFastPath.wide_decode_eligible."""
     mode = os.environ.get("PETALS_AMD_WIDE_DECODE", "off")
     if mode not in _WIDE_DECODE_MODES:
@@ -370,6 +371,8 @@ class _FastWeight:
             # 9..32 rows: the skinny-M MFMA kernel, same partials and epilogues
             return self.hip.gemm_nf4_skinny(self.packed, self.absmax, x, ws, residual, epilogue, 0, bias,
                                             self.absmax_t)
+        if self.quant == "mxfp4" and 8 < x.shape[0] <= WIDE_DECODE_MAX_ROWS:
+            return self.hip.gemm_mxfp4_skinny(self.mx_packed, self.mx_scales, x, ws, residual, epilogue, 0, bias)
         if self.quant == "nf4" and self.wg_waves > 1 and x.shape[0] <= _NF4_WG_MAX_BATCH:
             return self.hip.gemv_nf4(self.packed, self.absmax, x, ws, residual, epilogue, self.splits, bias,
                                      self.absmax_t, self.wg_waves, self.nt)
@@ -652,7 +655,7 @@ class LlamaFastPath(_TPFastPathMixin):
             self._ensure_rope(k_cache.shape[2])
             pos, kv_len = ctx.pos, ctx.kv_len
         if B > 8 and not self.wide_decode_eligible(B, adapter):
-            raise ValueError(f"decode_step: {B} rows need PETALS_AMD_WIDE_DECODE=on, NF4 weights, one GPU, no adapter")
+            raise ValueError(f"decode_step: {B} rows need PETALS_AMD_WIDE_DECODE=on, NF4 or MXFP4 weights, one GPU, no adapter")
         # wide steps (9..32 rows) keep S * rows <= 512 partial rows: the 8-row request covers them
         ws = _get_ws(self.device, "gemv", 64 * min(B, 8) * self._max_gemv_out())
 
@@ -727,15 +730,20 @@ class LlamaFastPath(_TPFastPathMixin):
 
     def wide_decode_eligible(self, rows: int, adapter=None) -> bool:
         """Steps of 9..32 rows the decode chain takes: wide mode on, every
-        weight NF4 (gemm_nf4_skinny), the dense Llama MLP, one GPU, no adapter
-        (lora_shrink / lora_reduce stop at 8 rows)."""
+        weight NF4 (gemm_nf4_skinny) or MXFP4 (gemm_mxfp4_skinny, which needs
+        every projection's out % 16 == 0), the dense Llama MLP, one GPU, no
+        adapter (lora_shrink / lora_reduce stop at 8 rows)."""
         return (
             8 < rows <= WIDE_DECODE_MAX_ROWS
-            and self.quant == "nf4"
+            and self.quant in ("nf4", "mxfp4")
             and self.multi_decode_supported
             and self.tp_world == 1
             and adapter is None
             and wide_decode_mode() == "on"
+            and (
+                self.quant == "nf4"
+                or all(w.out_dim % 16 == 0 for w in (self.wqkv_t, self.wo_t, self.wgateup_t, self.wdown_t))
+            )
         )
 
     def multi_decode_eligible(self, batch: int, tokens: int, adapter=None) -> bool:
