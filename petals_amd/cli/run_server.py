@@ -79,8 +79,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="decode steps under a LoRA adapter on Llama / Mixtral blocks: torch deltas around "
                              "each GEMV, or the fused shrink + expand-in-the-reduce kernels")
     parser.add_argument("--wide_decode", type=str, default="off", choices=["off", "on"],
-                        help="decode and multi-token steps of 9..32 rows on NF4 or MXFP4 Llama blocks: the prefill "
-                             "path (off) or the decode kernel chain on the format's skinny-M MFMA kernel (on)")
+                        help="decode and multi-token steps of 9..32 rows on NF4 or MXFP4 Llama blocks and NF4 "
+                             "Mixtral blocks: the prefill path (off) or the decode kernel chain on the format's "
+                             "skinny-M MFMA kernel (on)")
     parser.add_argument("--attn_cache_tokens", type=int, default=16384)
     parser.add_argument("--max_batch_size", type=int, default=8)
     parser.add_argument("--max_chunk_size_bytes", type=int, default=256 * 1024 * 1024,

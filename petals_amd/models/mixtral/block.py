@@ -112,6 +112,26 @@ class MixtralBlock(nn.Module):
                     self._fast, hidden_states, kv_cache[0], kv_cache[1], prefix_length, ctx=ctx,
                     max_b=min(8, 16 // max(self._fast.top_k, 1)),
                 )
+            if (
+                kv_cache is not None
+                and hidden_states.shape[1] == 1
+                and self._fast.wide_decode_eligible(hidden_states.shape[0])
+            ):
+                # opt-in (PETALS_AMD_WIDE_DECODE=on): 9..32 sequences on the
+                # decode kernel chain, NF4 experts on the expert-grouped
+                # skinny-M kernel (gemm_nf4_moe_skinny)
+                return self._fast.decode_step(
+                    hidden_states, kv_cache[0], kv_cache[1], prefix_length, ctx=ctx
+                )
+            if kv_cache is not None and hidden_states.shape[1] >= 2:
+                from petals_amd.ops.fused_decode import multi_decode_mode
+
+                # opt-in (PETALS_AMD_MULTI_DECODE=on): a short multi-token step,
+                # e.g. a speculative verify, on the decode kernel chain; up to
+                # 8 rows on the routed GEMVs, 9..32 rows with wide decode on
+                b, t = hidden_states.shape[:2]
+                if multi_decode_mode() == "on" and self._fast.multi_decode_eligible(b, t):
+                    return self._fast.decode_multi(hidden_states, kv_cache[0], kv_cache[1], prefix_length)
             return self._fast.forward(hidden_states, kv_cache, prefix_length)
 
         residual = hidden_states

@@ -17,7 +17,7 @@ SO_PATH = os.path.join(PKG_DIR, "_hip_ops.so")
 
 SOURCES = ["bindings.cpp", "elementwise.hip", "gemv.hip", "attention.hip", "nf4.hip", "int8.hip", "prefill_attn.hip", "moe.hip",
            "gemm_quant.hip", "mxfp4.hip", "attn_multi.hip", "attn_bwd.hip", "lora.hip", "nf4_skinny.hip",
-           "mxfp4_skinny.hip"]
+           "mxfp4_skinny.hip", "moe_skinny.hip"]
 
 
 def build(verbose: bool = False) -> str:

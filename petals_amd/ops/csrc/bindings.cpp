@@ -96,6 +96,12 @@ torch::Tensor gemm_mxfp4_skinny(
     c10::optional<torch::Tensor> residual, int64_t epilogue, int64_t splits_override,
     c10::optional<torch::Tensor> bias);
 int64_t gemm_mxfp4_skinny_splits(int64_t in_dim, int64_t out_dim, int64_t rows, int64_t splits_override);
+torch::Tensor gemm_nf4_moe_skinny(
+    torch::Tensor packed_all, torch::Tensor absmax_all, torch::Tensor x, torch::Tensor sel,
+    int64_t k_per_tok, torch::Tensor workspace, int64_t epilogue, int64_t splits_override,
+    c10::optional<torch::Tensor> absmax_t_all);
+int64_t gemm_nf4_moe_skinny_splits(int64_t in_dim, int64_t out_dim, int64_t rows, int64_t experts,
+                                   int64_t splits_override);
 torch::Tensor lora_shrink(torch::Tensor x, torch::Tensor a_cat);
 torch::Tensor lora_reduce(
     torch::Tensor partials, torch::Tensor t_part, torch::Tensor bt, std::vector<int64_t> segments,
@@ -224,6 +230,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_mxfp4_skinny_splits", &gemm_mxfp4_skinny_splits,
         "split count gemm_mxfp4_skinny uses for a shape (S * rows <= 512)",
         py::arg("in_dim"), py::arg("out_dim"), py::arg("rows"), py::arg("splits") = 0);
+  m.def("gemm_nf4_moe_skinny", &gemm_nf4_moe_skinny,
+        "wide Mixtral decode: x f32 [tokens, in] @ stacked NF4 experts, 1..64 virtual rows grouped by "
+        "expert on the device, each active expert streamed once through MFMA, split-K partials "
+        "[S, R, out] + the plain-f32 / swiglu-f32 epilogues",
+        py::arg("packed_all"), py::arg("absmax_all"), py::arg("x"), py::arg("sel"),
+        py::arg("k_per_tok"), py::arg("workspace"), py::arg("epilogue"), py::arg("splits") = 0,
+        py::arg("absmax_t_all") = py::none());
+  m.def("gemm_nf4_moe_skinny_splits", &gemm_nf4_moe_skinny_splits,
+        "split count gemm_nf4_moe_skinny uses for a shape (S * R <= 512)",
+        py::arg("in_dim"), py::arg("out_dim"), py::arg("rows"), py::arg("experts"), py::arg("splits") = 0);
   m.def("lora_shrink", &lora_shrink,
         "LoRA shrink for decode: x f32 [rows <= 8, in] . a_cat bf16 [R <= 256, in] -> split-K "
         "partials f32 [S, rows, R] (deterministic, no atomics)",

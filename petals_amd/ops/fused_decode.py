@@ -128,8 +128,8 @@ MULTI_DECODE_MAX_GQ = 16  # one 16-row MFMA group holds the q heads of a kv head
 
 
 def multi_decode_mode() -> str:
-    """How a Llama block runs a step of 2..8 new tokens against its KV cache (a
-    speculative-decoding verify step), read at call time from
+    """How a Llama or Mixtral block runs a step of 2..8 new tokens against its
+    KV cache (a speculative-decoding verify step), read at call time from
     PETALS_AMD_MULTI_DECODE: `off` (default) is the prefill path
     (LlamaFastPath.forward); `on` is the decode kernel chain on B*T rows with
     the causal multi-token attention kernel (LlamaFastPath.decode_multi)."""
@@ -177,12 +177,14 @@ WIDE_DECODE_MAX_ROWS = 32  # rows gemm_nf4_skinny / gemm_mxfp4_skinny take: two 
 
 
 def wide_decode_mode() -> str:
-    """How an NF4 or MXFP4 Llama block runs a decode or multi-token step of
-    9..32 rows, read at call time from PETALS_AMD_WIDE_DECODE: `off` (default)
-    is the prefill path (LlamaFastPath.forward); `on` is the decode kernel
-    chain with every projection on the format's skinny-M MFMA kernel
-    (csrc/nf4_skinny.hip, csrc/mxfp4_skinny.hip), see
-    LlamaFastPath.wide_decode_eligible."""
+    """How an NF4 or MXFP4 Llama block, or an NF4 Mixtral block, runs a decode
+    or multi-token step of 9..32 rows, read at call time from
+    PETALS_AMD_WIDE_DECODE: `off` (default) is the prefill path
+    (LlamaFastPath.forward); `on` is the decode kernel chain with every
+    projection on the format's skinny-M MFMA kernel (csrc/nf4_skinny.hip,
+    csrc/mxfp4_skinny.hip) and Mixtral's routed experts on the expert-grouped
+    one (csrc/moe_skinny.hip), see LlamaFastPath.wide_decode_eligible and
+    MixtralFastPath.wide_decode_eligible."""
     mode = os.environ.get("PETALS_AMD_WIDE_DECODE", "off")
     if mode not in _WIDE_DECODE_MODES:
         raise ValueError(
@@ -731,8 +733,9 @@ class LlamaFastPath(_TPFastPathMixin):
     def wide_decode_eligible(self, rows: int, adapter=None) -> bool:
         """Steps of 9..32 rows the decode chain takes: wide mode on, every
         weight NF4 (gemm_nf4_skinny) or MXFP4 (gemm_mxfp4_skinny, which needs
-        every projection's out % 16 == 0), the dense Llama MLP, one GPU, no
-        adapter (lora_shrink / lora_reduce stop at 8 rows)."""
+        every projection's out % 16 == 0), an MLP decode_multi covers, one GPU,
+        no adapter (lora_shrink / lora_reduce stop at 8 rows). MixtralFastPath
+        adds its experts' conditions."""
         return (
             8 < rows <= WIDE_DECODE_MAX_ROWS
             and self.quant in ("nf4", "mxfp4")

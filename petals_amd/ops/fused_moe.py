@@ -8,6 +8,12 @@ sync per step and the whole span is hipGraph-capturable (graph_safe) for the
 bf16, NF4 and int8 quantizations. Each selected expert's weights are read
 exactly once per token — the decode-time degenerate case of a grouped GEMM.
 
+Opt-in wide (PETALS_AMD_WIDE_DECODE=on, 9..32 rows) and multi-token
+(PETALS_AMD_MULTI_DECODE=on) steps run the same chain eagerly; past 16 routed
+rows NF4 experts go to gemm_nf4_moe_skinny (ops/csrc/moe_skinny.hip), which
+groups the rows by expert on the device and reads each active expert once per
+step.
+
 (The reference runs Mixtral experts densely inside one server's HF block with
 host-side routing: reference models/mixtral/block.py:73-81.)
 
@@ -33,6 +39,8 @@ from petals_amd.ops.fused_decode import (
 
 
 MOE_GEMM_MT = 32  # moe_gemm C-tile rows (ops/csrc/moe.hip MOE_MT)
+MOE_GEMV_MAX_ROWS = 16  # virtual rows (tokens * top_k) the per-row gemv_*_moe kernels take
+MOE_SKINNY_MAX_ROWS = 64  # virtual rows gemm_nf4_moe_skinny takes (ops/csrc/moe_skinny.hip)
 
 
 def moe_int8_mode() -> str:
@@ -109,8 +117,30 @@ class _StackedExperts:
         # keys by object id): multi-chunk prefills reuse each expert's dense form
         self._cache_keys = [_CacheKey() for _ in t_list]
 
+    absmax_t_all: Optional[torch.Tensor] = None
+
+    def _absmax_t(self) -> torch.Tensor:
+        """NF4 absmax transposed per expert, [E, out/64, in]: one 16-byte load
+        per k step in gemm_nf4_moe_skinny instead of 8 gathers. Built on the
+        first wide call (wide steps run eagerly, so allocating is safe) and
+        kept: it adds about 6 % to the experts' memory, which users who never
+        turn wide decode on do not pay."""
+        if self.absmax_t_all is None:
+            self.absmax_t_all = self.absmax_all.transpose(1, 2).contiguous()
+        return self.absmax_t_all
+
+    @property
+    def skinny_ok(self) -> bool:
+        """Shapes gemm_nf4_moe_skinny takes."""
+        return self.quant == "nf4" and self.in_dim % 32 == 0 and self.out_dim % 64 == 0
+
     def moe_gemv(self, x: torch.Tensor, sel: torch.Tensor, k_per_tok: int, ws: torch.Tensor,
                  epilogue: int) -> torch.Tensor:
+        if self.quant == "nf4" and sel.numel() > MOE_GEMV_MAX_ROWS:
+            # 17..64 virtual rows (wide decode): rows grouped by expert on the
+            # device, each active expert streamed once (csrc/moe_skinny.hip)
+            return self.hip.gemm_nf4_moe_skinny(self.packed_all, self.absmax_all, x, sel, k_per_tok, ws, epilogue,
+                                                0, self._absmax_t())
         if self.quant == "nf4":
             return self.hip.gemv_nf4_moe(self.packed_all, self.absmax_all, x, sel, k_per_tok, ws, epilogue)
         if self.quant == "int8":
@@ -158,7 +188,30 @@ class _StackedExperts:
 
 
 class MixtralFastPath(LlamaFastPath):
-    multi_decode_supported = False  # decode_multi runs the dense Llama MLP only
+    multi_decode_supported = True  # decode_multi / wide decode_step run _mlp_decode on the routed kernels
+
+    def wide_decode_eligible(self, rows: int, adapter=None) -> bool:
+        """Steps of 9..32 rows the decode chain takes: the base conditions
+        (wide mode on, one GPU, no adapter) plus stacked NF4 experts whose
+        rows * top_k virtual rows and shapes gemm_nf4_moe_skinny takes."""
+        return (
+            super().wide_decode_eligible(rows, adapter)
+            and self.quant == "nf4"
+            and self.stacked_gu is not None
+            and rows * self.top_k <= MOE_SKINNY_MAX_ROWS
+            and self.stacked_gu.skinny_ok
+            and self.stacked_down.skinny_ok
+        )
+
+    def multi_decode_eligible(self, batch: int, tokens: int, adapter=None) -> bool:
+        """The base conditions, with stacked experts (any format) and, for a
+        step within the GEMVs' 8 rows, virtual rows within gemv_*_moe's 16."""
+        rows = batch * tokens
+        return (
+            super().multi_decode_eligible(batch, tokens, adapter)
+            and self.stacked_gu is not None
+            and (rows * self.top_k <= MOE_GEMV_MAX_ROWS or self.wide_decode_eligible(rows, adapter))
+        )
 
     def _init_mlp_weights(self, block, hip_ops, quant):
         def t(w):

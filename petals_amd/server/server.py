@@ -217,10 +217,11 @@ class Server:
         if lora_decode == "fused":
             set_lora_decode_mode("fused")
         # decode and multi-token steps of 9..32 rows on NF4 or MXFP4 Llama
-        # blocks: "on" opts this PROCESS into the decode chain on the format's
-        # skinny-M MFMA kernel (ops/csrc/nf4_skinny.hip,
-        # ops/csrc/mxfp4_skinny.hip); "off" leaves the process setting
-        # (PETALS_AMD_WIDE_DECODE, default off) alone
+        # blocks and NF4 Mixtral blocks: "on" opts this PROCESS into the decode
+        # chain on the format's skinny-M MFMA kernel (ops/csrc/nf4_skinny.hip,
+        # ops/csrc/mxfp4_skinny.hip; Mixtral experts: ops/csrc/moe_skinny.hip);
+        # "off" leaves the process setting (PETALS_AMD_WIDE_DECODE, default
+        # off) alone
         from petals_amd.ops.fused_decode import _WIDE_DECODE_MODES, set_wide_decode_mode
 
         if wide_decode not in _WIDE_DECODE_MODES:
